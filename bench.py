@@ -12,16 +12,26 @@ data-path collective); one RCCL all-reduce of the statistics closes the job.
 
 Prints ONE JSON line (rank 0):
   value = images classified under faults per second, summed over ranks
+  ms_per_step = milliseconds per timed step (K = --steps of them)
   roofline = the dominant kernel (conv2, k_conv_cb16_x6 5x5) vs the peak of
              its engine (bf16x6 split: bf16 dense peak / 6), hipEvents around
-             its layer in the timed region; `contractions` = all conv / IP
-             layers vs their engines' peaks, timed over K further maps after
-             the timed region (events around 8 layers cost ~1 % of a step)
+             its layer in the timed region
   roofline_inject = the injection kernel vs HBM peak
-  cpu_baseline = Caffe CPU mode restated in C (oracle/caffe_cpu.c: per-image
-                 im2col + cblas_sgemm, Fail_cpu) over one full map, rank 0 at N=1.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the line.  What
+takes runs of its own is behind --full:
+  roofline.contractions = all conv / IP layers vs their engines' peaks, timed
+             over K further maps after the timed region (events around 8
+             layers cost ~1 % of a step)
+  cpu_baseline = Caffe CPU mode restated in C (oracle/caffe_cpu.c: per-image
+                 im2col + cblas_sgemm, Fail_cpu) over one full map, rank 0 at N=1
+             (the other workloads' CPU baselines and contraction tables too).
+
+--dump-outputs DIR writes what the last timed step computed (see
+collect_outputs) as DIR/<name>.npy after the timed steps; the inputs are the
+same from run to run for the same arguments.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
         torchrun --nproc-per-node N bench.py --gpus N ...  (one rank per GPU, RCCL)
 """
 from __future__ import annotations
@@ -119,6 +129,57 @@ def load_traffic():
         return {}
 
 
+DUMP_SAMPLE = 1 << 20   # most elements kept of a larger tensor (seeded indices): 4 MB per tensor in fp32
+DUMP_WEIGHTS = 12 << 20  # most elements kept of all faultable blobs together (48 MB in fp32)
+
+
+def sample_tensor(t, seed, cap=DUMP_SAMPLE):
+    """`t` flattened, whole if it has at most `cap` elements, else the
+    elements at `cap` indices drawn once from a generator seeded by `seed`
+    and the tensor's size (the same indices in every run and build)."""
+    import torch
+    t = t.detach().reshape(-1)
+    if t.numel() > cap:
+        g = torch.Generator().manual_seed(seed * 1000003 + t.numel() % 1000003)
+        t = t[torch.randint(t.numel(), (cap,), generator=g).to(t.device)]
+    return t.cpu().numpy()
+
+
+def collect_outputs(net, st, seed):
+    """What a caller of the timed Monte-Carlo path holds after its last map:
+    the net's output blobs and the classifier logits of that map, the
+    faultable weights as that map's injection left them (a seeded sample of
+    each blob), and the driver's records over the timed maps (per-map outputs,
+    broken cells per blob)."""
+    import numpy as np
+    arrays = {f"output_{name}": sample_tensor(t, seed) for name, t in net.outputs().items()}
+    if "fc8" in net.blob_names():
+        arrays["blob_fc8"] = sample_tensor(net.blob("fc8"), seed)
+    fps = net.failure_params()
+    for i, f in enumerate(fps):
+        arrays[f"faulted_weights_{i}"] = sample_tensor(f["data"], seed, min(DUMP_SAMPLE, DUMP_WEIGHTS // len(fps)))
+    arrays["per_map_outputs"] = np.asarray(st["per_map"], dtype=np.float32)
+    arrays["broken_cells"] = np.asarray(st["broken"], dtype=np.float64)
+    return arrays
+
+
+def write_outputs(dirpath, arrays, rank):
+    """DIR/<name>.npy, float32 or float64 (rank r > 0 of a multi-rank job: <name>.rank<r>.npy)."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        if total > 64 << 20:
+            raise RuntimeError(f"--dump-outputs: more than 64 MB of outputs at {name}")
+        name = name.replace("/", "_")                  # GoogLeNet's tops: loss1/loss1 -> loss1_loss1
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -127,7 +188,11 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--p-fault", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=1701)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the contraction table over K further maps and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--profile-layers", action="store_true", help="print the per-layer table to stderr")
     ap.add_argument("--no-conv-flip-cache", action="store_true",
                     help="training workloads: flip each convolution kernel per backward instead of taking the copy "
@@ -179,7 +244,9 @@ def main():
     if args.workload not in ("alexnet_mc", "alexnet_mc_reuse_prefix"):
         sys.path.insert(0, str(ROOT / "scripts"))
         from bench_workloads import run_workload
-        res = run_workload(args, world, rank, dev)
+        res, arrays = run_workload(args, world, rank, dev, collect_outputs if args.dump_outputs else None)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, arrays, rank)
         if rank == 0:
             print(json.dumps(res), flush=True)
         _finish(comm, distributed)
@@ -242,9 +309,13 @@ def main():
 
     # ---- roofline of the dominant kernel: live hipEvents of the timed region
     lt_timed = net.layer_times(reset=True)
-    # ---- contraction table: K further maps, untimed for `value`, with events
-    # around every conv / IP layer (each rank on its own maps, no collective)
-    if not args.profile_layers:
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, collect_outputs(net, st, args.seed), rank)
+    # ---- contraction table (--full): K further maps, untimed for `value`, with
+    # events around every conv / IP layer (each rank on its own maps, no collective)
+    if args.profile_layers:
+        lt = lt_timed
+    elif args.full:
         net.set_timing(2)
         for i in range(args.steps):
             step(args.warmup + args.steps + i)
@@ -252,7 +323,7 @@ def main():
         net.set_timing(False)
         lt = net.layer_times()
     else:
-        lt = lt_timed
+        lt = []
     flops = alexnet_gemm_table(args.batch)
     engines = alexnet_engines(args.batch)
     ran = {name for (name, typ, ms, cnt) in lt if name in flops and cnt > 0}   # prefix reuse: fc6-8 only
@@ -264,7 +335,7 @@ def main():
     # engine's peak; effective peak = total FLOPs / that minimum time
     peak_of = {"f32": MFMA_F32_PEAK_TFLOPS, "bf16x6": MFMA_X6_PEAK_TFLOPS}
     t_min = sum(f / (peak_of[engines[n]] * 1e12) for n, f in flops.items())
-    peak_tf = gemm_flops / t_min / 1e12
+    peak_tf = gemm_flops / t_min / 1e12 if t_min > 0 else 0.0
     layers = {name: {"engine": engines[name], "ms": round(ms / args.steps, 4),
                      "tflops": round(flops[name] / (ms / args.steps * 1e-3) / 1e12, 1) if ms > 0 else None}
               for (name, typ, ms, cnt) in lt if name in flops}
@@ -324,7 +395,7 @@ def main():
                      "algorithmic_bytes_per_launch": (dom_pmc["algorithmic_MB_per_step"] * 1e6
                                                       if dom_pmc.get("algorithmic_MB_per_step") else None),
                      "avg_us_per_launch": round(dom_ms * 1e3, 2),
-                     "contractions": {
+                     "contractions": None if not lt else {      # --full or --profile-layers
                          "achieved": round(achieved_tf, 2), "peak": round(peak_tf, 1), "unit": "TFLOP/s",
                          "frac": round(achieved_tf / peak_tf, 4) if peak_tf else None,
                          "frac_of_f32_mfma_peak": round(achieved_tf / MFMA_F32_PEAK_TFLOPS, 4),
@@ -347,7 +418,7 @@ def main():
         "mc_stats": {"maps": int(stats[len(st["sums"]) + 1].item()), "mean_outputs": mean_out,
                      "broken_cells": int(stats[len(st["sums"])].item())},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.batch, args.p_fault, args.seed)
     elif rank == 0:
         res["cpu_baseline"] = None

@@ -13,7 +13,7 @@ for r in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
     i=$((i + 1))
     envs=(); [ "$v" != "-" ] && read -ra envs <<< "$v"
-    timeout -k 10 300 env "${envs[@]}" python bench.py --no-cpu-baseline ${PROFILE_FLAG---profile-layers} --steps ${STEPS:-20} ${BENCH_ARGS:-} \
+    timeout -k 10 300 env "${envs[@]}" python bench.py --full --no-cpu-baseline ${PROFILE_FLAG---profile-layers} --steps ${STEPS:-20} ${BENCH_ARGS:-} \
       > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err || { tail -5 $O/v${i}_r$r.err; exit 1; }
     python3 - "$O/v${i}_r$r.json" "$v" <<'PY'
 import json, sys

@@ -202,7 +202,11 @@ def _graph_on():
     return os.environ.get("RRAM_MC_GRAPH", "0") != "0"
 
 
-def run_workload(args, world, rank, dev):
+def run_workload(args, world, rank, dev, collect=None):
+    """One workload's result line and, with `collect` (bench.py's
+    collect_outputs, --dump-outputs), the arrays its last timed step left.
+    The CPU baselines and the contraction table that takes maps of its own
+    run only with args.full."""
     import torch
     import torch.distributed as dist
     from rramsim import caffe, make_inject_cfg, models
@@ -235,14 +239,16 @@ def run_workload(args, world, rank, dev):
             acc += [sum(r[k] for r in rows), sum(r[k] * r[k] for r in rows)]
         tot_m = allreduce_stats(acc + [len(rows)], dev)
         per_output = {name: map_statistics(tot_m[2 * k], tot_m[2 * k + 1], tot_m[-1]) for k, name in enumerate(names)}
-        # the contraction table: events around every conv / IP layer over K
+        arrays = collect(net, dict(st, per_map=rows), args.seed) if collect else None
+        # the contraction table (--full): events around every conv / IP layer over K
         # further maps after the timed region (the maps run eager while timed)
-        net.layer_times(reset=True)
-        net.set_timing(2)
-        for i in range(args.steps):
-            mc.run((rank + world * (args.warmup + args.steps + i)) * maps_per_step, maps_per_step)
-        torch.cuda.synchronize()
-        net.set_timing(0)
+        if args.full:
+            net.layer_times(reset=True)
+            net.set_timing(2)
+            for i in range(args.steps):
+                mc.run((rank + world * (args.warmup + args.steps + i)) * maps_per_step, maps_per_step)
+            torch.cuda.synchronize()
+            net.set_timing(0)
         tot = allreduce_stats(st["sums"] + [st["maps"]], dev)
         n_maps = world * args.steps * maps_per_step
         res = _base("Monte Carlo fault maps/sec, CIFAR-10 quick (quantised + lognormal)", "maps/s", n_maps / el,
@@ -252,15 +258,15 @@ def run_workload(args, world, rank, dev):
         res["hipgraph"] = graph
         res["mc_mean_outputs"] = [x / max(tot[-1], 1) for x in tot[:-1]]
         res["mc_timed_maps"] = per_output     # mean, sample std and 95 % CI half-width over the timed maps
-        res["roofline"] = contraction_roofline(net, args.steps * maps_per_step, net.layer_times())
+        res["roofline"] = contraction_roofline(net, args.steps * maps_per_step, net.layer_times() if args.full else None)
         mc.close()
         net.close()
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             cb = mc_cpu_baseline(models.cifar10_quick, "cifar10_quick", batch, cfgs, args.seed)
             cb.update(value=round(cb["value"] / batch, 4), unit="maps/s",
                       images_per_s=cb["value"])   # the metric is maps/s: one map = one `batch`-image pass
             res["cpu_baseline"] = cb
-        return res
+        return res, arrays
 
     if args.workload == "lenet_mc":
         batch = 100
@@ -279,11 +285,13 @@ def run_workload(args, world, rank, dev):
                     maps_per_step=maps_per_step * world, p_fault=args.p_fault)
         res["mc_mean_outputs"] = [x / max(tot[-1], 1) for x in tot[:-1]]
         res["hipgraph"] = mc.graph_active()
+        rows = st["per_map"][args.warmup * maps_per_step:(args.warmup + args.steps) * maps_per_step]
+        arrays = collect(net, dict(st, per_map=rows), args.seed) if collect else None
         mc.close()
         net.close()
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = lenet_cpu_baseline(batch, args.p_fault, args.seed)
-        return res
+        return res, arrays
 
     if args.workload in ("cifar10_full_train", "lenet_train"):
         if args.workload == "cifar10_full_train":
@@ -311,6 +319,8 @@ def run_workload(args, world, rank, dev):
                                 f"{'C++ host P2PSync (librram_caffe RCCL)' if dp.sync is not None else 'torch.distributed ' + dist.get_backend() if _dist_on() else 'no collective'})")
         res["broken_cells"] = sum(dp.solver.broken_counts())
         res["hipgraph"] = dp.solver.graph_active()
+        # the last iteration's net outputs and the weights it left (a seeded sample of each faultable blob)
+        arrays = collect(dp.solver.net, dict(per_map=[], broken=dp.solver.broken_counts()), args.seed) if collect else None
         # training roofline over the whole iteration: forward + weight-gradient +
         # data-gradient contractions (the first layer computes no data gradient;
         # the backward GEMMs run on the fp32 MFMA engine), against the step time
@@ -329,7 +339,7 @@ def run_workload(args, world, rank, dev):
                                      "contractions (fp32 MFMA) of the Convolution / InnerProduct layers over the "
                                      "step time (includes the LRN / pool / loss / update / Fail kernels and the "
                                      "launch gaps of a batch-100 net)"}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             # a CPU training iteration costs more than its TEST-phase forward:
             # the forward-only Caffe-CPU rate bounds the CPU training rate from above
             name = args.workload.split("_train")[0] if args.workload == "lenet_train" else "cifar10_full"
@@ -339,7 +349,7 @@ def run_workload(args, world, rank, dev):
                             + cb["sample"])
             res["cpu_baseline"] = cb
         dp.close()
-        return res
+        return res, arrays
 
     if args.workload == "googlenet_sweep":
         batch = args.batch
@@ -372,11 +382,16 @@ def run_workload(args, world, rank, dev):
                     world, args, el, workload="googlenet_sweep_0.1-10pct", model="GoogLeNet (train_val TEST)",
                     global_batch=batch * world, rates=rates)
         res["sweep"] = sweep
+        # the last map of the last fault rate, and every rate's per-map outputs over the timed steps
+        arrays = None
+        if collect:
+            rows = [r for mc in mcs for r in mc.stats()["per_map"][args.warmup:args.warmup + args.steps]]
+            arrays = collect(net, dict(mcs[-1].stats(), per_map=rows), args.seed)
         res["roofline"] = contraction_roofline(net, args.steps * len(rates), net.layer_times())
         for mc in mcs:
             mc.close()
         net.close()
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = mc_cpu_baseline(models.googlenet, "googlenet", batch, cfgs_for(0.01), args.seed)
-        return res
+        return res, arrays
     raise ValueError(args.workload)

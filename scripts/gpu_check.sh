@@ -17,7 +17,7 @@ for r in csv.DictReader(open(sys.argv[1])):
         print("  ", r["Name"][:70], r["Calls"], round(float(r["AverageNs"]) / 1e3, 1))
 PY
 for c in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $R/$O/pmc_chk/p_$c -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $R/$O/pmc_chk_$c.log 2>&1 ) || { echo "pmc $c failed"; tail -5 $O/pmc_chk_$c.log; exit 1; }
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $R/$O/pmc_chk/p_$c -o run -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $R/$O/pmc_chk_$c.log 2>&1 ) || { echo "pmc $c failed"; tail -5 $O/pmc_chk_$c.log; exit 1; }
 done
 python3 scripts/pmc_traffic.py $O/pmc_chk > $O/pmc_chk_traffic.json && python3 -c "
 import json; d=json.load(open('$O/pmc_chk_traffic.json'))

@@ -12,6 +12,6 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE" \
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $R/$OUT/p$i -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $R/$OUT/p$i.log 2>&1 || { echo "pass $i failed rc=$?"; exit 1; }
+  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $R/$OUT/p$i -o run -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $R/$OUT/p$i.log 2>&1 || { echo "pass $i failed rc=$?"; exit 1; }
 done
 echo pmc done

@@ -1,6 +1,6 @@
 """HBM traffic of the bench's dominant kernels from rocprofv3 --pmc passes
 (scripts/pmc.sh output: one pass with FETCH_SIZE, one with WRITE_SIZE, over
-`bench.py --steps 3 --warmup 1`).
+`bench.py --steps 3 --warmup 1 --full`).
 
 Corrections (MI355X_MICROARCH.md, HBM section): FETCH_SIZE / WRITE_SIZE are
 in KiB; on gfx950 FETCH_SIZE reports half the bytes of a wide coalesced

@@ -169,7 +169,7 @@ def test_bench_two_ranks_rehearsal(device, workload):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(root / "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload]
     if workload == "alexnet_mc":
-        cmd += ["--batch", "64"]
+        cmd += ["--batch", "64", "--full"]               # --full: the CPU baseline, which N > 1 leaves out
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

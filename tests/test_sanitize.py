@@ -24,7 +24,8 @@ ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "rram-caffe-simulation_amd"
 DRIVER = PKG / "build_asan" / "parse_fuzz"
 GOLD = ROOT / "tests" / "golden"
-REF = Path("/root/reference")
+# optional: a checkout of the reference project, whose own config files are then parsed too
+REF = Path(os.environ["RRAM_REFERENCE_DIR"]) if os.environ.get("RRAM_REFERENCE_DIR") else None
 
 
 @pytest.fixture(scope="module")
@@ -81,7 +82,7 @@ def test_prototxts_under_asan_ubsan(driver, tmp_path):
         p = tmp_path / f"{name}.prototxt"
         p.write_text(t)
         paths.append(p)
-    if REF.exists():                                    # the reference's own config files, when present
+    if REF is not None and REF.exists():                # the reference's own config files, when given
         for rel in ("examples/mnist/lenet_train_test.prototxt", "examples/cifar10/cifar10_quick_train_test.prototxt",
                     "examples/cifar10/cifar10_full_train_test.prototxt", "models/bvlc_alexnet/train_val.prototxt",
                     "models/bvlc_googlenet/train_val.prototxt",
