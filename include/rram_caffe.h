@@ -256,6 +256,26 @@ int rram_mc_set_reuse_prefix(rram_mc_t mc, int enable);
 int rram_mc_set_graph(rram_mc_t mc, int enable);
 int rram_mc_graph_active(rram_mc_t mc, int* active);
 int rram_mc_inject_times(rram_mc_t mc, double* ms, long* launches, int64_t* weights, int reset);
+/* Map batching (opt-in, for launch-bound small nets; no reference
+ * counterpart): K fault maps share every launch of one forward.  The net must
+ * have been built at batch K * B; map j of a group of K consecutive map ids
+ * evaluates images [j B, (j + 1) B) of the batch against its own faulted copy
+ * of every faultable blob (one rram_inject_rng_maps launch per group), the
+ * InnerProduct layers run rram_ip_fwd_groups and the loss / accuracy heads
+ * fold one value per map, in map order.  With the K slices holding the same B
+ * images (rram_mc_tile_inputs copies the first slice of every source top over
+ * the others) the statistics are the sequential driver's at batch B, bit for
+ * bit.  A short last group injects and folds only its live maps.  Fails,
+ * naming the cause, when a source batch is not divisible by K, a source
+ * advances between forwards (HDF5Data), a statistic mixes images
+ * (EuclideanLoss), a faultable blob is a Convolution's, a convolution's plan
+ * differs between the two batch sizes, or prefix reuse / graph replay is on
+ * (which likewise fail while K > 1).  K = 1 restores the sequential driver.
+ * rram_mc_map_stack: the K faulted copies of faultable blob i ([K][count],
+ * NULL while K = 1) as the last group left them. */
+int rram_mc_set_map_batch(rram_mc_t mc, int K);
+int rram_mc_tile_inputs(rram_mc_t mc);
+int rram_mc_map_stack(rram_mc_t mc, int i, float** data, int64_t* count, int* map_batch);
 
 /* ------------------------------------------------------ multi-GPU (RCCL)
  * The reference's P2PSync (include/caffe/parallel.hpp; src/caffe/parallel.cpp:

@@ -163,6 +163,15 @@ int rram_inject_rng_batched_dev(const rram_inject_seg* segs, int nsegs, uint64_t
                                 const uint32_t* map_id_dev, unsigned long long* counters,
                                 rram_stream_t stream);
 
+/* Map batching: nmaps faulted copies of every segment in one launch.  Copy j
+ * of segment i is written to segs[i].w_out + j * out_strides[i] (elements;
+ * >= n) with map id map_begin + j: the bits of nmaps rram_inject_rng_batched
+ * calls.  w_clean is read once per element; counters[i] += the broken cells
+ * of all nmaps copies. */
+int rram_inject_rng_maps(const rram_inject_seg* segs, int nsegs, uint64_t seed, uint32_t map_begin, int nmaps,
+                         const int64_t* out_strides, unsigned long long* counters, rram_stream_t stream);
+
+
 /* Monte-Carlo statistics of one map in one launch (the MC analogue of
  * Solver::Test's score accumulation, src/caffe/solver.cpp:410-430):
  * sums[k] += p[k][0] and per_map_row[k] = p[k][0] (per_map_row nullable). */
@@ -387,6 +396,13 @@ int rram_conv_output_octets_only(const rram_conv_desc* d);
  * (0 = tiles run across images), LDS patch pieces per wave.  Returns 1 with
  * the plan filled, 0 when the octet kernel does not take d. */
 int rram_conv_octet_plan(const rram_conv_desc* d, int* plan);
+/* The fp32 engine's implicit-GEMM forward picks its split-K count from num.
+ * num > 0 pins that choice to the plan of a batch of `num` images for every
+ * later forward of a larger batch (0: each call's own num, the default), so
+ * an image's result at batch K * num is its result at batch num, bit for bit
+ * (MonteCarlo map batching sets it around its convolutions' forwards).
+ * Process-wide, like rram_set_inject_grid; returns the previous value. */
+int rram_set_conv_plan_num(int num);
 /* oct = the octet companion of x (channels % 8 == 0). */
 int rram_pack_octets(const float* x, void* oct, int num, int channels, int height, int width,
                      rram_stream_t stream);
@@ -464,6 +480,26 @@ size_t rram_ip_rows_pack_bytes(int M, int N, int K, size_t ws_bytes, int* rows_p
 int rram_ip_fwd_rows(const float* x, const void* x_rows, const float* w, const float* bias, float* y, void* y_rows,
                      int y_rows_per_tile, int M, int N, int K, int relu, void* ws, size_t ws_bytes,
                      int* y_rows_written, rram_stream_t stream);
+
+/* Map groups: G InnerProduct forwards that share launches.  Group g computes
+ * rram_ip_fwd(x + g*M*K, w + g*w_group_stride, bias + g*bias_group_stride,
+ * y + g*M*N, M, N, K, ...) (strides in elements; bias_group_stride may be 0
+ * for a shared bias) and the result is that loop's, bit for bit.  Where the
+ * fp32 engine serves the shape it is one GEMM launch with the group in the
+ * grid's z -- the tile, split-K count and chunk chosen for M, not G*M -- plus
+ * at most one split-K reduce over the G*M*N outputs, or one GEMV launch over
+ * G when M = 1.  It loops over rram_ip_fwd for shapes the bf16x6 engine
+ * serves (its packed operands are per call), when ws_bytes cannot hold G
+ * groups of split-K partials (the split is never changed), and when the
+ * groups' operand alignments differ.  The packed-rows fc6 -> fc7 chain
+ * (rram_ip_fwd_rows) has no grouped form.
+ * rram_ip_fwd_groups_fused: 1 when the call would be one GEMM launch (plus at
+ * most one reduce), 0 when it would loop (16-byte aligned operands assumed). */
+int rram_ip_fwd_groups(const float* x, const float* w, int64_t w_group_stride, const float* bias,
+                       int64_t bias_group_stride, float* y, int G, int M, int N, int K, int transpose, int relu,
+                       void* ws, size_t ws_bytes, rram_stream_t stream);
+int rram_ip_fwd_groups_fused(int G, int M, int N, int K, int transpose, size_t ws_bytes);
+
 /* dw += ..., db += ... (nullable), dx = ... (nullable). */
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw,
                 float* db, float* dx, int M, int N, int K, int transpose,
@@ -588,6 +624,20 @@ int rram_accuracy(const float* x, const float* label, float* correct_out,
  * rram_softmax_loss_fwd_acc; acc_sum requires ratio). */
 int rram_accuracy_acc(const float* x, const float* label, float* correct, float* count, float* ratio, int outer,
                       int C, int inner, int top_k, int ignore, float* acc_sum, float* acc_row, rram_stream_t s);
+
+/* Map groups: the _acc entries on G slices of `outer` rows each, one block
+ * per group, out[g] / correct[g] / count[g] / ratio[g] the ungrouped entry's
+ * bits for slice g.  The Monte-Carlo fold is made afterwards by one thread in
+ * group order: acc_sum += v_g, acc_rows[g * row_stride] = v_g (acc_rows
+ * nullable) for g < live (<= G; a short last group).  Heads too large for the
+ * one-block accuracy plan run rram_accuracy_acc once per group. */
+int rram_softmax_loss_fwd_groups(const float* prob, const float* label, float* out, int G, int outer, int C,
+                                 int inner, int ignore, float* acc_sum, float* acc_rows, int64_t row_stride, int live,
+                                 rram_stream_t stream);
+int rram_accuracy_groups(const float* x, const float* label, float* correct, float* count, float* ratio, int G,
+                         int outer, int C, int inner, int top_k, int ignore, float* acc_sum, float* acc_rows,
+                         int64_t row_stride, int live, rram_stream_t stream);
+
 /* EuclideanLoss (euclidean_loss_layer.cu:9-38): diff = a - b,
  * loss_out[0] = sum(diff^2) / num / 2 (device scalar, the layer's top);
  * backward dx = alpha * diff with alpha = +-loss_weight / num. */

@@ -26,6 +26,13 @@ int col2im_core(const float* col, int64_t ldcol, int nimg, const rram_conv_desc*
                 int64_t im_img, int accumulate, hipStream_t s);
 int gemv_core(int trans, int M, int N, float alpha, const float* A, const float* x, float beta,
               float* y, hipStream_t s);
+std::atomic<int>& conv_plan_num();
+int gemm_groups_fused(int G, int M, int N, int K, bool have_ws, size_t ws_bytes);
+int gemm_groups_core(int G, int trans_b, int M, int N, int K, const float* A, int64_t grp_a, const float* B, int ldb,
+                     int64_t grp_b, float* C, int64_t grp_c, const float* bias, int64_t grp_bias, int relu, void* ws,
+                     size_t ws_bytes, hipStream_t s);
+int gemv_groups_core(int G, int N, int K, const float* W, int64_t grp_w, const float* x, const float* bias,
+                     int64_t grp_bias, int relu, float* y, hipStream_t s);
 int release_conv_tables();
 std::atomic<uint64_t>& scratch_gen();
 int pack_octets(const float* x, void* oct, int num, int C, int HWi, hipStream_t s);
@@ -492,6 +499,44 @@ int rram_ip_fwd(const float* x, const float* w, const float* bias, float* y, int
                      ws_bytes, as_stream(s));
   return gemm_core(0, 1, M, N, K, 1.0f, x, K, w, K, 0.0f, y, N, bias, RRAM_BIAS_COL, relu, ws,
                    ws_bytes, as_stream(s));
+}
+
+int rram_set_conv_plan_num(int num) {
+  RRAM_REQUIRE(num >= 0, "set_conv_plan_num: negative batch");
+  return conv_plan_num().exchange(num);
+}
+
+int rram_ip_fwd_groups_fused(int G, int M, int N, int K, int transpose, size_t ws_bytes) {
+  RRAM_REQUIRE(G >= 0 && M >= 0 && N >= 0 && K >= 0, "ip_fwd_groups: negative size");
+  if (M == 1 && !transpose) return 1;  // the GEMV plan: one launch over G
+  if (!transpose && rram_f32_engine_for_ip(M, N, K, ws_bytes) == RRAM_ENGINE_BF16X6) return 0;
+  return gemm_groups_fused(G, M, N, K, ws_bytes > 0, ws_bytes);
+}
+
+int rram_ip_fwd_groups(const float* x, const float* w, int64_t w_group_stride, const float* bias,
+                       int64_t bias_group_stride, float* y, int G, int M, int N, int K, int transpose, int relu,
+                       void* ws, size_t ws_bytes, rram_stream_t s) {
+  RRAM_REQUIRE(G >= 0 && M >= 0 && N >= 0 && K >= 0, "ip_fwd_groups: negative size");
+  RRAM_REQUIRE(w_group_stride >= 0 && bias_group_stride >= 0, "ip_fwd_groups: negative group stride");
+  if (G == 0 || M == 0 || N == 0) return RRAM_OK;
+  RRAM_REQUIRE(x && w && y, "ip_fwd_groups: NULL");
+  const size_t wsb = ws != nullptr ? ws_bytes : 0;
+  if (M == 1 && !transpose)
+    return gemv_groups_core(G, N, K, w, w_group_stride, x, bias, bias_group_stride, relu, y, as_stream(s));
+  // the bf16x6 engine's shapes loop (its packed operands and partials are per call)
+  if (transpose || rram_f32_engine_for_ip(M, N, K, wsb) != RRAM_ENGINE_BF16X6) {
+    const int rc = gemm_groups_core(G, transpose ? 0 : 1, M, N, K, x, (int64_t)M * K, w, transpose ? N : K,
+                                    w_group_stride, y, (int64_t)M * N, bias, bias_group_stride, relu, ws, wsb,
+                                    as_stream(s));
+    if (rc != 0) return rc < 0 ? rc : RRAM_OK;
+  }
+  for (int g = 0; g < G; ++g) {
+    const int rc = rram_ip_fwd(x + (int64_t)g * M * K, w + g * w_group_stride,
+                               bias ? bias + g * bias_group_stride : nullptr, y + (int64_t)g * M * N, M, N, K,
+                               transpose, relu, ws, ws_bytes, s);
+    if (rc) return rc;
+  }
+  return RRAM_OK;
 }
 
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw, float* db, float* dx,

@@ -399,6 +399,68 @@ __global__ void __launch_bounds__(256)
   if (cur >= 0) block_count_flush(nb, counters ? counters + cur : nullptr);
 }
 
+// k_inject_batched for nmaps consecutive maps in one launch (map batching):
+// copy j of segment s is drawn with map id map_begin + j, exactly
+// k_inject_batched's draw for that (seed, map, layer, index), and stored at
+// dst + j * stride[s].  Every clean element is loaded once and stays in
+// registers across the j loop; the broken-cell count of a segment is summed
+// over its copies.
+struct InjectMapStrides {
+  int64_t s[RRAM_MAX_SEGS];  // elements between two copies of a segment
+};
+template <bool FAST>
+__global__ void __launch_bounds__(256)
+    k_inject_maps(InjectSegs segs, InjectMapStrides strides, uint64_t seed, uint32_t map_begin, int nmaps,
+                  unsigned long long* counters) {
+  const int64_t total = segs.chunk_start[segs.nsegs];
+  const int64_t per = (total + gridDim.x - 1) / gridDim.x;
+  const int64_t cbeg = blockIdx.x * per;
+  const int64_t cend = cbeg + per < total ? cbeg + per : total;
+  int cur = -1;
+  unsigned nb = 0;
+  int s = 0;
+  for (int64_t c = cbeg; c < cend; ++c) {
+    while (c >= segs.chunk_start[s + 1]) ++s;
+    if (s != cur) {
+      if (cur >= 0) block_count_flush(nb, counters ? counters + cur : nullptr);
+      nb = 0;
+      cur = s;
+    }
+    const InjectSeg& g = segs.s[s];
+    const int64_t stride = strides.s[s];
+    const int64_t begin = (c - segs.chunk_start[s]) * kInjChunk;
+    const int64_t end = min(begin + (int64_t)kInjChunk, g.n);
+    if (aligned16(g.src) && aligned16(g.dst) && (stride & 3) == 0) {
+      const int64_t nv = (end - begin) >> 2;
+      const float4* s4 = reinterpret_cast<const float4*>(g.src + begin);
+      float4 buf[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t q = threadIdx.x + u * 256;
+        if (q < nv) buf[u] = s4[q];
+      }
+      for (int j = 0; j < nmaps; ++j) {
+        float4* d4 = reinterpret_cast<float4*>(g.dst + j * stride + begin);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int64_t q = threadIdx.x + u * 256;
+          if (q < nv) d4[q] = inject4<FAST>(buf[u], begin + 4 * q, seed, map_begin + j, g, nb);
+        }
+      }
+      for (int64_t i = begin + 4 * nv + threadIdx.x; i < end; i += 256) {
+        const float w = g.src[i];
+        for (int j = 0; j < nmaps; ++j) g.dst[j * stride + i] = inject1<FAST>(w, i, seed, map_begin + j, g, nb);
+      }
+    } else {
+      for (int64_t i = begin + threadIdx.x; i < end; i += 256) {
+        const float w = g.src[i];
+        for (int j = 0; j < nmaps; ++j) g.dst[j * stride + i] = inject1<FAST>(w, i, seed, map_begin + j, g, nb);
+      }
+    }
+  }
+  if (cur >= 0) block_count_flush(nb, counters ? counters + cur : nullptr);
+}
+
 // Monte-Carlo statistics of one map: sums[k] += out_k[0]; per_map[k] = out_k[0].
 __global__ void k_mc_accumulate(rram_mc_outputs o, float* __restrict__ sums, float* __restrict__ per_map) {
   const int k = threadIdx.x;
@@ -844,6 +906,44 @@ int rram_inject_rng_batched_dev(const rram_inject_seg* segs, int nsegs, uint64_t
                                 unsigned long long* counters, rram_stream_t s) {
   RRAM_REQUIRE(map_id_dev != nullptr, "inject_dev: map_id_dev is NULL");
   return rram::inject_batched_core(segs, nsegs, seed, 0, map_id_dev, counters, s);
+}
+
+int rram_inject_rng_maps(const rram_inject_seg* segs, int nsegs, uint64_t seed, uint32_t map_begin, int nmaps,
+                         const int64_t* out_strides, unsigned long long* counters, rram_stream_t s) {
+  using namespace rram;
+  RRAM_REQUIRE(nsegs >= 0 && nsegs <= RRAM_MAX_SEGS, "inject_maps: nsegs out of range");
+  RRAM_REQUIRE(nmaps >= 0, "inject_maps: nmaps < 0");
+  if (nsegs == 0 || nmaps == 0) return RRAM_OK;
+  RRAM_REQUIRE(segs && out_strides, "inject_maps: segs / out_strides is NULL");
+  InjectSegs is{};
+  InjectMapStrides st{};
+  is.nsegs = nsegs;
+  bool fast = true;
+  for (int i = 0; i < nsegs; ++i) {
+    const int rc = check_cfg(&segs[i].cfg);
+    if (rc) return rc;
+    RRAM_REQUIRE(segs[i].n >= 0, "inject_maps: segment %d n < 0", i);
+    if (segs[i].n > 0) RRAM_REQUIRE(segs[i].w_clean && segs[i].w_out, "inject_maps: segment %d NULL", i);
+    RRAM_REQUIRE(segs[i].layer_id < (1u << 28), "inject_maps: layer_id must be < 2^28");
+    RRAM_REQUIRE(nmaps == 1 || out_strides[i] >= segs[i].n, "inject_maps: segment %d copies overlap (stride < n)", i);
+    is.s[i] = make_inject_seg(segs[i].w_clean, segs[i].w_out, segs[i].n, segs[i].layer_id, segs[i].cfg);
+    st.s[i] = out_strides[i];
+    is.chunk_start[i + 1] = is.chunk_start[i] + (segs[i].n + kInjChunk - 1) / kInjChunk;
+    fast = fast && is.s[i].mode == 0;
+  }
+  const int64_t total = is.chunk_start[nsegs];
+  if (total == 0) return RRAM_OK;
+  const int64_t grid_cap = inject_grid().load(std::memory_order_relaxed) > 0
+                               ? static_cast<int64_t>(inject_grid().load(std::memory_order_relaxed))
+                               : static_cast<int64_t>(kInjectGrid);
+  const int grid = static_cast<int>(total < grid_cap ? total : grid_cap);
+  if (fast)
+    hipLaunchKernelGGL(k_inject_maps<true>, dim3(grid), dim3(kThreads), 0, as_stream(s), is, st, seed, map_begin,
+                       nmaps, counters);
+  else
+    hipLaunchKernelGGL(k_inject_maps<false>, dim3(grid), dim3(kThreads), 0, as_stream(s), is, st, seed, map_begin,
+                       nmaps, counters);
+  return launch_status("inject_maps");
 }
 }  // extern "C"
 

@@ -374,7 +374,14 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
   int kbeg = 0, kend = P.K;
   float* part = nullptr;
   if (P.split > 1) {
-    kbeg = z * P.k_chunk;
+    int zs = z;
+    if (P.zgroups > 1) {  // map groups: z = group * split + zs, the partial slabs in z order
+      const int g = z / P.split;
+      zs = z - g * P.split;
+      va.p += g * P.grp_a;
+      vb.p += g * P.grp_b;
+    }
+    kbeg = zs * P.k_chunk;
     kend = min(P.K, kbeg + P.k_chunk);
     part = P.ws + (int64_t)z * P.M * P.N;
   } else if (z > 0) {  // conv group
@@ -793,7 +800,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   int kbeg = 0, kend = P.K;
   float* part = nullptr;
   if (P.split > 1) {
-    kbeg = z * P.k_chunk;
+    int zs = z;
+    if (P.zgroups > 1) {  // map groups: z = group * split + zs, the partial slabs in z order
+      const int g = z / P.split;
+      zs = z - g * P.split;
+      va.p += g * P.grp_a;
+      vb.p += g * P.grp_b;
+    }
+    kbeg = zs * P.k_chunk;
     kend = min(P.K, kbeg + P.k_chunk);
     part = P.ws + (int64_t)z * P.M * P.N;
   } else if (z > 0) {  // conv group
@@ -1354,8 +1368,11 @@ int launch_cfg(Params P, int gz, hipStream_t s) {
 // padded rows of M (AlexNet: conv1 M = 96, conv4 M = 192 per group) as long as
 // the grid keeps >= 2 blocks per CU; 64x64 when even that grid is too small.
 // force_big: split-K grids (128x128).
+// pz (0: gz): the z extent the tile policy sees; the map-group GEMM
+// (gemm_groups_core) launches gz = groups and keeps one group's tiles (pz = 1).
 template <int AM, int BMODE, int OM, int KB>
-int launch(const Params& P, int gz, hipStream_t s, bool force_big) {
+int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
+  if (pz <= 0) pz = gz;
   if (force_big) {
 #ifndef RRAM_SPLIT_THIN32
 #define RRAM_SPLIT_THIN32 1
@@ -1385,7 +1402,7 @@ int launch(const Params& P, int gz, hipStream_t s, bool force_big) {
   // conv3 (507 such tiles, one round) 0.70 -> 0.69 ms is within noise, and
   // conv4 / conv5 / conv1 (fewer tiles or M % 128 != 0) are slower, so they
   // keep the policy below.
-  if (KB == 16 && P.M % 128 == 0 && (int64_t)(P.M / 128) * ((P.N + 255) / 256) * gz >= 1024)
+  if (KB == 16 && P.M % 128 == 0 && (int64_t)(P.M / 128) * ((P.N + 255) / 256) * pz >= 1024)
     return launch_cfg<2, 2, 2, 4, AM, BMODE, OM, KB>(P, gz, s);
   const int64_t ntn = (P.N + 127) / 128;
   const int cands[4] = {128, 192, 96, 64};  // ties keep 128 (2 blocks per CU)
@@ -1393,16 +1410,16 @@ int launch(const Params& P, int gz, hipStream_t s, bool force_big) {
   int64_t best_pad = -1;
   for (int c : cands) {
     const int64_t tiles_m = (P.M + c - 1) / c;
-    if (tiles_m * ntn * gz < 512 && c != 64) continue;
+    if (tiles_m * ntn * pz < 512 && c != 64) continue;
     const int64_t pad = tiles_m * c - P.M;
     if (best_pad < 0 || pad < best_pad) {
       best = c;
       best_pad = pad;
     }
   }
-  if (KB == 16 && P.M % 128 != 0 && P.M % 64 == 0 && ntn * (P.M / 64) * gz >= 512)
+  if (KB == 16 && P.M % 128 != 0 && P.M % 64 == 0 && ntn * (P.M / 64) * pz >= 512)
     best = 64;  // e.g. M = 192: three unpadded 64-row tiles beat one 192-row tile at KB = 16
-  if (best == 64 && ntn * ((P.M + 63) / 64) * gz < 256)
+  if (best == 64 && ntn * ((P.M + 63) / 64) * pz < 256)
     return launch_cfg<2, 2, 1, 1, AM, BMODE, OM, KB>(P, gz, s);  // 64 x 64: twice the blocks
   switch (best) {
     case 192: return launch_cfg<2, 2, 3, 2, AM, BMODE, OM, KB>(P, gz, s);  // 192 x 128
@@ -1449,7 +1466,7 @@ int conv_kb(int K) {
   return K >= 1024 ? 16 : 32;
 }
 
-int dispatch(int am, int bm, int om, const Params& P, int gz, hipStream_t s, bool force_big = false) {
+int dispatch(int am, int bm, int om, const Params& P, int gz, hipStream_t s, bool force_big = false, int pz = 0) {
   if (gemm2_ok(am, bm, P)) {
     if (om == OUT_ROWMAJOR) return launch2<KCV, KCV, OUT_ROWMAJOR>(P, gz, s);
   }
@@ -1467,7 +1484,7 @@ int dispatch(int am, int bm, int om, const Params& P, int gz, hipStream_t s, boo
     if (am == KCV) return launch<KCV, CONVT64, OUT_NCHW, 16>(P, gz, s, force_big);
   }
 #define RRAM_D(A_, B_, O_) \
-  if (am == A_ && bm == B_ && om == O_) return launch<A_, B_, O_, 32>(P, gz, s, force_big);
+  if (am == A_ && bm == B_ && om == O_) return launch<A_, B_, O_, 32>(P, gz, s, force_big, pz);
   RRAM_D(KC, KC, OUT_ROWMAJOR)
   RRAM_D(KCV, KC, OUT_ROWMAJOR)
   RRAM_D(KC, KCV, OUT_ROWMAJOR)
@@ -1602,6 +1619,7 @@ int release_conv_tables() {
 int gemm_x6_nt(int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb, float beta,
                float* C, int ldc, const float* bias, int bias_mode, int relu, void* ws, size_t ws_bytes,
                hipStream_t s, const void* a_rows = nullptr, char* y_rows = nullptr, int y_bmc = 0);
+void gemm_split_plan(int M, int N, int K, bool have_ws, size_t ws_bytes, int& split_out, int& chunk_out);
 
 int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const float* A, int lda,
               const float* B, int ldb, float beta, float* C, int ldc, const float* bias,
@@ -1631,6 +1649,26 @@ int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const 
   int bm = trans_b ? KC : RC;
   if (am == KC && vec_ok(A, lda, K)) am = KCV;
   if (bm == KC && vec_ok(B, ldb, K)) bm = KCV;
+  int split = 1, chunk = K;
+  gemm_split_plan(M, N, K, ws != nullptr, ws_bytes, split, chunk);
+  if (split > 1) {
+    P.split = split;
+    P.k_chunk = chunk;
+    P.ws = static_cast<float*>(ws);
+    int rc = dispatch(am, bm, OUT_ROWMAJOR, P, split, s, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s,
+                       P.ws, split, M, N, P.e);
+    return launch_status("gemm splitk reduce");
+  }
+  return dispatch(am, bm, OUT_ROWMAJOR, P, 1, s);
+}
+
+// The split-K plan of gemm_core's fp32 kernel for an [M][N] output over K:
+// split = 1 (chunk = K) or the number of K chunks and their length (a
+// multiple of BK).  Shared with gemm_groups_core, whose groups must split
+// exactly as one gemm_core call of a group does.
+void gemm_split_plan(int M, int N, int K, bool have_ws, size_t ws_bytes, int& split_out, int& chunk_out) {
   // split-K when the 128x128 grid is far below the CU count and K is long
   const int64_t tiles = (int64_t)((N + 127) / 128) * ((M + 127) / 128);
   int split = 1;
@@ -1642,26 +1680,133 @@ int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const 
   // 1-4: 1024; 256 since LeNet ip1 / ip2, K = 800 / 500: a lone workgroup
   // walking K is all latency, profiles/r04_ab_tail_batched.txt)
   constexpr int mink = 256;
-  if (ws != nullptr && tiles < target && K >= mink) {
+  if (have_ws && tiles < target && K >= mink) {
     split = static_cast<int>(target / (tiles > 0 ? tiles : 1));
     if (split > target / 16) split = target / 16;
     while (split > 1 && (K / split) < std::min(256, mink / 2)) --split;
     while (split > 1 && (size_t)split * M * N * sizeof(float) > ws_bytes) --split;
   }
+  int chunk = K;
   if (split > 1) {
-    int chunk = (K + split - 1) / split;
+    chunk = (K + split - 1) / split;
     chunk = (chunk + BK - 1) / BK * BK;
     split = (K + chunk - 1) / chunk;
+  }
+  split_out = split;
+  chunk_out = split > 1 ? chunk : K;
+}
+
+// The operand modes gemm_core picks for C = A . op(B) with row-major A [M][K]
+void gemm_groups_modes(const float* A, int lda, const float* B, int ldb, int trans_b, int K, int& am, int& bm) {
+  am = vec_ok(A, lda, K) ? KCV : KC;
+  bm = trans_b ? (vec_ok(B, ldb, K) ? KCV : KC) : RC;
+}
+
+// 1 when gemm_groups_core would run G groups as one fp32-kernel launch (plus
+// at most one reduce): the split-K plan the shape wants (its plan with an
+// ample workspace) is the plan it gets, and all G groups' partials fit
+// ws_bytes.  A workspace that would cut the split, or hold fewer than G
+// groups of partials, means a loop (the split is never changed to fit).  The
+// bf16x6 engine's shapes and pointer alignment are the caller's checks.
+int gemm_groups_fused(int G, int M, int N, int K, bool have_ws, size_t ws_bytes) {
+  int want = 1, chunk = K;
+  gemm_split_plan(M, N, K, true, ~static_cast<size_t>(0), want, chunk);
+  if (want == 1) return 1;
+  return have_ws && (size_t)std::max(G, 1) * want * M * N * sizeof(float) <= ws_bytes ? 1 : 0;
+}
+
+// G independent products C_g = act(A_g . op(B_g) + bias_g) in one launch of
+// gemm_core's fp32 kernel: group g's operands are A + g * grp_a, B + g * grp_b,
+// C + g * grp_c, bias + g * grp_bias (grp_bias may be 0).  The tile, the
+// split-K count and chunk are those gemm_core picks for one group (M, not
+// G * M), the group rides in the grid's z (z = g * split + s), group g's
+// partials are slabs [g * split, (g + 1) * split) of ws, and one reduce walks
+// the G * M * N outputs in k_splitk_reduce's order: the bits of G gemm_core
+// calls.  Returns 1 when it ran, 0 when the caller must loop (the groups'
+// operand alignments differ, or ws is too small for G groups of partials),
+// < 0 on error.
+int gemm_groups_core(int G, int trans_b, int M, int N, int K, const float* A, int64_t grp_a, const float* B, int ldb,
+                     int64_t grp_b, float* C, int64_t grp_c, const float* bias, int64_t grp_bias, int relu, void* ws,
+                     size_t ws_bytes, hipStream_t s) {
+  if (G <= 0 || M == 0 || N == 0) return 1;
+  RRAM_REQUIRE(C != nullptr && (K == 0 || (A && B)), "gemm groups: NULL");
+  int am = 0, bm = 0;
+  gemm_groups_modes(A, K, B, ldb, trans_b, K, am, bm);
+  for (int g = 1; g < G; ++g) {
+    int a2 = 0, b2 = 0;
+    gemm_groups_modes(A + g * grp_a, K, B + g * grp_b, ldb, trans_b, K, a2, b2);
+    if (a2 != am || b2 != bm) return 0;
+  }
+  if (!gemm_groups_fused(G, M, N, K, ws != nullptr, ws_bytes)) return 0;
+  Params P{};
+  P.a = make_view(A, K, M, K);
+  P.b = make_view(B, ldb, N, K);
+  P.e = make_epi(C, N, 1.0f, 0.0f, bias, RRAM_BIAS_COL, relu);
+  P.M = M;
+  P.N = N;
+  P.K = K;
+  P.split = 1;
+  P.k_chunk = K;
+  P.grp_a = grp_a;
+  P.grp_b = grp_b;
+  P.grp_c = grp_c;
+  P.grp_bias = grp_bias;
+  int split = 1, chunk = K;
+  gemm_split_plan(M, N, K, ws != nullptr, ws_bytes, split, chunk);
+  if (split > 1) {
     P.split = split;
     P.k_chunk = chunk;
     P.ws = static_cast<float*>(ws);
-    int rc = dispatch(am, bm, OUT_ROWMAJOR, P, split, s, true);
+    P.zgroups = G;
+    int rc = dispatch(am, bm, OUT_ROWMAJOR, P, G * split, s, true, split);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s,
-                       P.ws, split, M, N, P.e);
-    return launch_status("gemm splitk reduce");
+    hipLaunchKernelGGL(k_splitk_reduce_groups, dim3(stream_blocks((int64_t)G * M * N)), dim3(256), 0, s, P.ws, split, M,
+                       N, P.e, G, grp_c, grp_bias);
+    rc = launch_status("gemm groups splitk reduce");
+    return rc ? rc : 1;
   }
-  return dispatch(am, bm, OUT_ROWMAJOR, P, 1, s);
+  const int rc = dispatch(am, bm, OUT_ROWMAJOR, P, G, s, false, 1);  // z = group (the conv-group path)
+  return rc ? rc : 1;
+}
+
+// G GEMVs (rram_ip_fwd's M = 1 plan) in one launch: y_g[N] = act(W_g x_g +
+// bias_g), one wave per output, each output k_gemv's sum (alpha = 1, beta = 0),
+// then k_bias_add's and k_relu_fwd's expressions on it
+__global__ void __launch_bounds__(256) k_gemv_groups(int G, int N, int K, const float* __restrict__ W, int64_t grp_w,
+                                                     const float* __restrict__ x, const float* __restrict__ bias,
+                                                     int64_t grp_bias, int relu, float* __restrict__ y) {
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const int nw = (gridDim.x * blockDim.x) >> 6;
+  for (int go = wave; go < G * N; go += nw) {
+    const int g = go / N, o = go - g * N;
+    const float* A = W + g * grp_w;
+    const float* xg = x + (int64_t)g * K;
+    float s = 0.0f;
+    for (int r = lane; r < K; r += 64) {
+      const float a = A[(int64_t)o * K + r];
+      s += a * xg[r];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) {
+      float v = 1.0f * s + 0.0f;
+      if (bias) v += bias[g * grp_bias + o];
+      if (relu) v = v > 0.0f ? v : v * 0.0f;
+      y[(int64_t)g * N + o] = v;
+    }
+  }
+}
+
+int gemv_groups_core(int G, int N, int K, const float* W, int64_t grp_w, const float* x, const float* bias,
+                     int64_t grp_bias, int relu, float* y, hipStream_t s) {
+  if (G <= 0 || N == 0) return RRAM_OK;
+  RRAM_REQUIRE(W && x && y, "gemv groups: NULL");
+  const int64_t outs = (int64_t)G * N;
+  RRAM_REQUIRE(outs < (1ll << 31), "gemv groups: too many outputs");
+  const int blocks = static_cast<int>(std::min<int64_t>((outs + 3) / 4, 4096));
+  hipLaunchKernelGGL(k_gemv_groups, dim3(blocks), dim3(256), 0, s, G, N, K, W, grp_w, x, bias, grp_bias, relu, y);
+  return launch_status("gemv groups");
 }
 
 
@@ -1790,8 +1935,17 @@ int conv_patch_fwd(const rram_conv_desc* d, const float* w, Params& P, hipStream
 // rows x 128 positions, split toward 1024 workgroups (512 / 2048 measured
 // slower, profiles/r04_ab_conv_split.txt and the round-4 sweep of
 // scripts/r04/gpu_r04_aq.sh) with >= 128 K per split
+// rram_set_conv_plan_num: the batch the split is planned for (0: d->num).
+// MonteCarlo map batching runs K groups of B images in one call and pins the
+// plan to B, so an image's partial sums are those of the batch-B call.
+std::atomic<int>& conv_plan_num() {
+  static std::atomic<int> v{0};
+  return v;
+}
 int conv_fwd_split(const rram_conv_desc* d, int M, int N, int K) {
   constexpr int target = 1024;
+  const int pn = conv_plan_num().load(std::memory_order_relaxed);
+  if (pn > 0 && pn < d->num) N = pn * d->out_h * d->out_w;
   if (d->group != 1 || M > 64 || K < 256) return 1;
   const int64_t tiles = (int64_t)((M + 31) / 32) * ((N + 127) / 128);
   if (tiles >= 256) return 1;

@@ -102,6 +102,7 @@ struct Params {
   int64_t grp_bias;
   int split;                 // number of K splits (z = split when > 1)
   int tiles_m, tiles_n, tiles_z;
+  int zgroups;               // map groups under split-K (z = group * split + s; 0 / 1: none)
 };
 
 // Per-thread constant data of the B loader for the CONV view.
@@ -345,6 +346,30 @@ __global__ void __launch_bounds__(256) k_splitk_reduce(const float* __restrict__
     if (ep.beta != 0.0f) o += ep.beta * *dst;
     if (ep.bias_mode == RRAM_BIAS_ROW) o += ep.bias[m];
     else if (ep.bias_mode == RRAM_BIAS_COL) o += ep.bias[n];
+    if (ep.relu) o = fmaxf(o, 0.0f);
+    *dst = o;
+  }
+}
+
+// k_splitk_reduce over `groups` independent [M][N] outputs in one launch
+// (rram_ip_fwd_groups): group g's partials are slabs [g * split, (g + 1) *
+// split) of ws, its output ep.C + g * grp_c, its bias ep.bias + g * grp_bias;
+// every element is k_splitk_reduce's expression on the same operands
+__global__ void __launch_bounds__(256) k_splitk_reduce_groups(const float* __restrict__ ws, int split, int M, int N,
+                                                              Epi ep, int groups, int64_t grp_c, int64_t grp_bias) {
+  const int64_t total = (int64_t)M * N;
+  for (int64_t gi = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gi < total * groups;
+       gi += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t g = gi / total, idx = gi - g * total;
+    const float s = splitk_sum(ws + g * split * total, split, total, idx);
+    const int m = static_cast<int>(idx / N);
+    const int n = static_cast<int>(idx - (int64_t)m * N);
+    float* dst = ep.C + g * grp_c + (int64_t)m * ep.ldc + n;
+    const float* bias = ep.bias ? ep.bias + g * grp_bias : nullptr;
+    float o = ep.alpha * s;
+    if (ep.beta != 0.0f) o += ep.beta * *dst;
+    if (ep.bias_mode == RRAM_BIAS_ROW) o += bias[m];
+    else if (ep.bias_mode == RRAM_BIAS_COL) o += bias[n];
     if (ep.relu) o = fmaxf(o, 0.0f);
     *dst = o;
   }

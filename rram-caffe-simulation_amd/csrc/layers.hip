@@ -628,10 +628,9 @@ __global__ void __launch_bounds__(256) k_softmax_reg(const float* __restrict__ x
 // softmax_loss_layer.cpp:95-112 (single block, deterministic)
 // acc_sum / acc_row (nullable): the MonteCarlo statistics of this output
 // (k_mc_accumulate's sum += v, row = v) written by the thread that stores v
-__global__ void __launch_bounds__(1024) k_softmax_loss_fwd(const float* __restrict__ prob,
-                                                           const float* __restrict__ label,
-                                                           float* out, int outer, int C, int inner,
-                                                           int ignore, float* acc_sum, float* acc_row) {
+__device__ __forceinline__ void softmax_loss_block(const float* __restrict__ prob, const float* __restrict__ label,
+                                                   float* out, int outer, int C, int inner, int ignore,
+                                                   float* acc_sum, float* acc_row) {
   __shared__ float sl[16], sc[16];
   float loss = 0.0f, cnt = 0.0f;
   const int64_t cols = (int64_t)outer * inner;
@@ -663,6 +662,37 @@ __global__ void __launch_bounds__(1024) k_softmax_loss_fwd(const float* __restri
     if (acc_sum) *acc_sum += v;
     if (acc_row) *acc_row = v;
   }
+}
+__global__ void __launch_bounds__(1024) k_softmax_loss_fwd(const float* __restrict__ prob,
+                                                           const float* __restrict__ label,
+                                                           float* out, int outer, int C, int inner,
+                                                           int ignore, float* acc_sum, float* acc_row) {
+  softmax_loss_block(prob, label, out, outer, C, inner, ignore, acc_sum, acc_row);
+}
+// Map groups: block g runs k_softmax_loss_fwd's block on slice g of the batch
+// (outer rows each) and writes out[g]; the statistics are folded afterwards,
+// in group order (k_fold_groups)
+__global__ void __launch_bounds__(1024) k_softmax_loss_fwd_groups(const float* __restrict__ prob,
+                                                                  const float* __restrict__ label, float* out,
+                                                                  int outer, int C, int inner, int ignore) {
+  const int64_t g = blockIdx.x;
+  softmax_loss_block(prob + g * outer * C * inner, label + g * outer * inner, out + g, outer, C, inner, ignore,
+                     nullptr, nullptr);
+}
+// The Monte-Carlo fold of G per-group values, by one thread and in group
+// order (sums is a float running sum): acc_sum += v_g and acc_rows[g *
+// row_stride] = v_g (acc_rows nullable) for g = 0 .. live - 1, the same adds
+// the sequential maps' kernels make one launch at a time
+__global__ void k_fold_groups(const float* __restrict__ vals, int live, float* acc_sum, float* acc_rows,
+                              int64_t row_stride) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float s = *acc_sum;
+  for (int g = 0; g < live; ++g) {
+    const float v = vals[g];
+    s += v;
+    if (acc_rows) acc_rows[g * row_stride] = v;
+  }
+  *acc_sum = s;
 }
 
 // k_softmax_loss_fwd + k_softmax_loss_bwd in one block (TRAIN phase, small
@@ -902,9 +932,10 @@ __global__ void __launch_bounds__(256) k_accuracy_fused(const float* __restrict_
 // block reduction, then correct / count / ratio written directly — no memsets,
 // no atomics, no second launch.
 constexpr int kAccSmall = 1 << 16;
-__global__ void __launch_bounds__(1024) k_accuracy_small(const float* __restrict__ x, const float* __restrict__ label,
-                                                         float* correct, float* count, float* ratio, int outer, int C,
-                                                         int inner, int top_k, int ignore, float* acc_sum, float* acc_row) {
+__device__ __forceinline__ void accuracy_small_block(const float* __restrict__ x, const float* __restrict__ label,
+                                                     float* correct, float* count, float* ratio, int outer, int C,
+                                                     int inner, int top_k, int ignore, float* acc_sum,
+                                                     float* acc_row) {
   __shared__ int sa[16], sc[16];
   const int cols = outer * inner;
   int hits = 0, cnt = 0;
@@ -945,6 +976,21 @@ __global__ void __launch_bounds__(1024) k_accuracy_small(const float* __restrict
     if (acc_sum) *acc_sum += v;
     if (acc_row) *acc_row = v;
   }
+}
+__global__ void __launch_bounds__(1024) k_accuracy_small(const float* __restrict__ x, const float* __restrict__ label,
+                                                         float* correct, float* count, float* ratio, int outer, int C,
+                                                         int inner, int top_k, int ignore, float* acc_sum, float* acc_row) {
+  accuracy_small_block(x, label, correct, count, ratio, outer, C, inner, top_k, ignore, acc_sum, acc_row);
+}
+// Map groups: block g runs k_accuracy_small's block on slice g (outer rows
+// each) and writes correct[g], count[g], ratio[g]; folded by k_fold_groups
+__global__ void __launch_bounds__(1024) k_accuracy_small_groups(const float* __restrict__ x,
+                                                                const float* __restrict__ label, float* correct,
+                                                                float* count, float* ratio, int outer, int C,
+                                                                int inner, int top_k, int ignore) {
+  const int64_t g = blockIdx.x;
+  accuracy_small_block(x + g * outer * C * inner, label + g * outer * inner, correct + g, count + g, ratio + g, outer,
+                       C, inner, top_k, ignore, nullptr, nullptr);
 }
 
 __global__ void k_accuracy_ratio(const float* correct, const float* count, float* ratio, float* acc_sum,
@@ -1221,6 +1267,21 @@ int rram_softmax_loss_fwd_acc(const float* prob, const float* label, float* out,
   return launch_status("softmax_loss_fwd");
 }
 
+int rram_softmax_loss_fwd_groups(const float* prob, const float* label, float* out, int G, int outer, int C,
+                                 int inner, int ignore, float* acc_sum, float* acc_rows, int64_t row_stride, int live,
+                                 rram_stream_t s) {
+  RRAM_REQUIRE(G >= 0 && outer >= 0 && C > 0 && inner > 0 && out, "softmax_loss_fwd_groups: bad args");
+  RRAM_REQUIRE(outer == 0 || (prob && label), "softmax_loss_fwd_groups: NULL");
+  RRAM_REQUIRE(live >= 0 && live <= G, "softmax_loss_fwd_groups: live outside [0, G]");
+  RRAM_REQUIRE(acc_rows == nullptr || acc_sum != nullptr, "softmax_loss_fwd_groups: acc_rows without acc_sum");
+  if (G == 0) return RRAM_OK;
+  hipLaunchKernelGGL(k_softmax_loss_fwd_groups, dim3(G), dim3(1024), 0, as_stream(s), prob, label, out, outer, C,
+                     inner, ignore);
+  if (acc_sum != nullptr && live > 0)
+    hipLaunchKernelGGL(k_fold_groups, dim3(1), dim3(64), 0, as_stream(s), out, live, acc_sum, acc_rows, row_stride);
+  return launch_status("softmax_loss_fwd_groups");
+}
+
 int rram_softmax_loss_fwd_bwd(const float* prob, const float* label, float* out, float* dx, int outer, int C,
                               int inner, int ignore, float loss_weight, rram_stream_t s) {
   RRAM_REQUIRE(outer >= 0 && C > 0 && inner > 0 && out, "softmax_loss_fwd_bwd: bad args");
@@ -1289,6 +1350,35 @@ int rram_accuracy_acc(const float* x, const float* label, float* correct, float*
   if (ratio)
     hipLaunchKernelGGL(k_accuracy_ratio, dim3(1), dim3(1), 0, as_stream(s), correct, count, ratio, acc_sum, acc_row);
   return launch_status("accuracy");
+}
+
+int rram_accuracy_groups(const float* x, const float* label, float* correct, float* count, float* ratio, int G,
+                         int outer, int C, int inner, int top_k, int ignore, float* acc_sum, float* acc_rows,
+                         int64_t row_stride, int live, rram_stream_t s) {
+  RRAM_REQUIRE(G >= 0 && outer >= 0 && C > 0 && inner > 0 && top_k >= 1 && correct && count && ratio,
+               "accuracy_groups: bad args");
+  RRAM_REQUIRE(outer == 0 || (x && label), "accuracy_groups: NULL");
+  RRAM_REQUIRE(live >= 0 && live <= G, "accuracy_groups: live outside [0, G]");
+  RRAM_REQUIRE(acc_rows == nullptr || acc_sum != nullptr, "accuracy_groups: acc_rows without acc_sum");
+  if (G == 0) return RRAM_OK;
+  const int64_t cols = (int64_t)outer * inner;
+  if (!(cols * C <= kAccSmall && C <= 64)) {
+    // the large heads take rram_accuracy_acc's multi-block plans: one call per
+    // group, each folding its own value (stream order is group order)
+    for (int g = 0; g < G; ++g) {
+      const bool fold = acc_sum != nullptr && g < live;
+      const int rc = rram_accuracy_acc(x + (int64_t)g * cols * C, label + (int64_t)g * cols, correct + g, count + g,
+                                       ratio + g, outer, C, inner, top_k, ignore, fold ? acc_sum : nullptr,
+                                       fold && acc_rows ? acc_rows + g * row_stride : nullptr, s);
+      if (rc) return rc;
+    }
+    return RRAM_OK;
+  }
+  hipLaunchKernelGGL(k_accuracy_small_groups, dim3(G), dim3(1024), 0, as_stream(s), x, label, correct, count, ratio,
+                     outer, C, inner, top_k, ignore);
+  if (acc_sum != nullptr && live > 0)
+    hipLaunchKernelGGL(k_fold_groups, dim3(1), dim3(64), 0, as_stream(s), ratio, live, acc_sum, acc_rows, row_stride);
+  return launch_status("accuracy_groups");
 }
 
 int rram_i32_to_f32(const int* x, float* y, int64_t n, rram_stream_t s) {

@@ -764,6 +764,27 @@ int rram_mc_set_graph(rram_mc_t m, int enable) {
     m->mc->set_graph(enable != 0);
   });
 }
+int rram_mc_set_map_batch(rram_mc_t m, int K) {
+  return guarded([&] {
+    NEED(m);
+    m->mc->set_map_batch(K);
+  });
+}
+int rram_mc_tile_inputs(rram_mc_t m) {
+  return guarded([&] {
+    NEED(m);
+    m->mc->TileInputs();
+  });
+}
+int rram_mc_map_stack(rram_mc_t m, int i, float** data, int64_t* count, int* map_batch) {
+  return guarded([&] {
+    NEED(m);
+    if (i < 0 || i >= m->mc->num_fault_blobs()) throw Error("rram_mc_map_stack: blob index out of range");
+    if (data) *data = const_cast<float*>(m->mc->map_stack(i));
+    if (count) *count = m->mc->fault_blob_count(i);
+    if (map_batch) *map_batch = m->mc->map_batch();
+  });
+}
 int rram_mc_graph_active(rram_mc_t m, int* active) {
   return guarded([&] {
     NEED(m);

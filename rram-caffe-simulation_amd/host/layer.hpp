@@ -115,7 +115,23 @@ class Layer {
   // *sum += top, *row = top (row nullable) in the kernel that stores the top,
   // so the MC driver launches no accumulate kernel.  sum == nullptr clears it;
   // false: the layer cannot (the driver then accumulates itself).
-  virtual bool set_top_accumulator(float* /*sum*/, float* /*row*/) { return false; }
+  // Map groups (below): row is the first live group's row, group g's row is
+  // row + g * row_stride, and only the first `live` groups (-1: all) are
+  // folded, in group order.
+  virtual bool set_top_accumulator(float* /*sum*/, float* /*row*/, int64_t /*row_stride*/ = 0, int /*live*/ = -1) {
+    return false;
+  }
+  // MonteCarlo map batching (MonteCarlo::set_map_batch, TEST phase): the batch
+  // axis carries K groups of num / K images, one fault map each.  A layer that
+  // has to know where one group ends accepts K > 1: InnerProduct (group g
+  // multiplies by copy g of each faulted blob: group_params[j] is the K-copy
+  // stack of blobs()[j], strides[j] elements apart, or nullptr for the layer's
+  // own unfaulted blob), SoftmaxWithLoss and Accuracy (their scalar top becomes
+  // {K}, one value per group).  Per-image layers keep the default and run
+  // unchanged.  K == 1 undoes it.  Backward of a grouped layer throws.
+  virtual bool set_map_groups(int K, const Dtype* const* /*group_params*/, const int64_t* /*strides*/) {
+    return K == 1;
+  }
   // TEST-phase Concat fold (Net::Net): a producer whose top only feeds a
   // channel Concat writes its output straight into the Concat top at a
   // channel offset (write_into_concat: true when it can), and the Concat then

@@ -233,6 +233,15 @@ template <typename Dtype>
 void ConvolutionLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bottom,
                                           const std::vector<Blob<Dtype>*>& top) {
   CAFFE_CHECK(bottom[0] != top[0], this->name() << ": in-place convolution is not allowed");
+  // map groups: plan the fp32 engine's split-K for one group's images (restored on every exit)
+  struct PlanNum {
+    const bool on;
+    const int prev;
+    explicit PlanNum(int n) : on(n > 0), prev(on ? rram_set_conv_plan_num(n) : 0) {}
+    ~PlanNum() {
+      if (on) rram_set_conv_plan_num(prev);
+    }
+  } plan_num(groups_ > 1 ? desc_.num / groups_ : 0);
   const int shp[4] = {desc_.num, desc_.channels, desc_.height, desc_.width};
   const void* xo = nullptr;
   if (want_in_oct_) {
@@ -324,6 +333,7 @@ void ConvolutionLayer<Dtype>::Backward_gpu(const std::vector<Blob<Dtype>*>& top,
   const bool db = bias_term_ && this->param_propagate_down(1);
   const bool dx = pd.size() > 0 && pd[0];
   if (!dw && !db && !dx) return;
+  CAFFE_CHECK(groups_ == 1, this->name() << ": backward through map groups is not supported (inference only)");
   const size_t need = rram_conv2d_bwd_workspace(&desc_, 1);
   // chunk up to 256 images per col buffer (bounded at 1 GiB), plus the
   // weight-gradient split-K partials (64 before round 4: CIFAR conv2 at b100
@@ -381,7 +391,7 @@ void InnerProductLayer<Dtype>::Reshape(const std::vector<Blob<Dtype>*>& bottom,
   // reduce: fc6 -> fc7), key = (M, K, rows per tile)
   in_rows_key_ = 0;
   int bmc = 0;
-  const size_t rb = (this->phase_ == TEST && !transpose_)
+  const size_t rb = (this->phase_ == TEST && !transpose_ && groups_ == 1)
                         ? rram_ip_rows_pack_bytes(M_, N_, K_, ws_request(), &bmc)
                         : 0;
 #ifndef RRAM_IP_ROWS  // A/B builds: 0 = every InnerProduct packs its own input
@@ -398,6 +408,15 @@ template <typename Dtype>
 void InnerProductLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bottom,
                                            const std::vector<Blob<Dtype>*>& top) {
   void* ws = Caffe::workspace(ws_request());
+  if (groups_ > 1) {  // map groups: no packed-row shortcut (rram_ip_fwd_groups has no rows form)
+    CAFFE_CHECK(M_ % groups_ == 0, this->name() << ": " << M_ << " rows do not split into " << groups_ << " map groups");
+    const Dtype* w = group_param_[0] ? group_param_[0] : this->blobs_[0]->gpu_data();
+    const Dtype* b = !bias_term_ ? nullptr : group_param_[1] ? group_param_[1] : this->blobs_[1]->gpu_data();
+    RRAM_CALL(rram_ip_fwd_groups(bottom[0]->gpu_data(), w, group_stride_[0], b, group_stride_[1],
+                                 top[0]->mutable_gpu_data(), groups_, M_ / groups_, N_, K_, transpose_ ? 1 : 0,
+                                 fused_relu ? 1 : 0, ws, Caffe::workspace_size(), Caffe::stream()));
+    return;
+  }
   // the packed-row companions (TEST, Reshape): read the input's when its
   // producer wrote it, write the output's when the consumer asked
   const void* xr = in_rows_key_ ? bottom[0]->data()->valid_rows(in_rows_key_) : nullptr;
@@ -424,6 +443,7 @@ template <typename Dtype>
 void InnerProductLayer<Dtype>::Backward_gpu(const std::vector<Blob<Dtype>*>& top,
                                             const std::vector<bool>& pd,
                                             const std::vector<Blob<Dtype>*>& bottom) {
+  CAFFE_CHECK(groups_ == 1, this->name() << ": backward through map groups is not supported (inference only)");
   RRAM_CALL(rram_ip_bwd(bottom[0]->gpu_data(), this->blobs_[0]->gpu_data(), top[0]->gpu_diff(),
                         this->param_propagate_down(0) ? this->blobs_[0]->mutable_gpu_diff() : nullptr,
                         (bias_term_ && this->param_propagate_down(1)) ? this->blobs_[1]->mutable_gpu_diff() : nullptr,
@@ -766,13 +786,21 @@ class SoftmaxWithLossLayer : public Layer<Dtype> {
   }
   void Reshape(const std::vector<Blob<Dtype>*>& bottom, const std::vector<Blob<Dtype>*>& top) override {
     prob_.ReshapeLike(*bottom[0]);
-    top[0]->Reshape({});
+    if (groups_ > 1) top[0]->Reshape({groups_});
+    else top[0]->Reshape({});
     if (top.size() > 1) top[1]->ReshapeLike(*bottom[0]);
   }
-  bool set_top_accumulator(float* sum, float* row) override {
+  bool set_top_accumulator(float* sum, float* row, int64_t row_stride = 0, int live = -1) override {
     if (this->phase_ == TRAIN && sum) return false;  // the TRAIN head (loss + dx in one launch) has no fold
     acc_sum_ = sum;
     acc_row_ = sum ? row : nullptr;
+    acc_stride_ = row_stride;
+    acc_live_ = live;
+    return true;
+  }
+  bool set_map_groups(int K, const Dtype* const*, const int64_t*) override {
+    if (K > 1 && this->phase_ != TEST) return false;
+    groups_ = K > 1 ? K : 1;
     return true;
   }
 
@@ -786,7 +814,12 @@ class SoftmaxWithLossLayer : public Layer<Dtype> {
     // (Backward then has nothing left to do; writing it when no backward
     // follows is harmless: nothing else writes this diff)
     dx_in_fwd_ = this->phase_ == TRAIN && (int64_t)o * c * i <= 65536;
-    if (dx_in_fwd_)
+    if (groups_ > 1) {
+      CAFFE_CHECK(o % groups_ == 0, this->name() << ": " << o << " rows do not split into " << groups_ << " map groups");
+      RRAM_CALL(rram_softmax_loss_fwd_groups(prob_.gpu_data(), bottom[1]->gpu_data(), top[0]->mutable_gpu_data(),
+                                             groups_, o / groups_, c, i, ignore_, acc_sum_, acc_row_, acc_stride_,
+                                             acc_live_ < 0 ? groups_ : std::min(acc_live_, groups_), Caffe::stream()));
+    } else if (dx_in_fwd_)
       RRAM_CALL(rram_softmax_loss_fwd_bwd(prob_.gpu_data(), bottom[1]->gpu_data(), top[0]->mutable_gpu_data(),
                                           bottom[0]->mutable_gpu_diff(), o, c, i, ignore_, this->loss(0),
                                           Caffe::stream()));
@@ -800,6 +833,7 @@ class SoftmaxWithLossLayer : public Layer<Dtype> {
   void Backward_gpu(const std::vector<Blob<Dtype>*>&, const std::vector<bool>& pd,
                     const std::vector<Blob<Dtype>*>& bottom) override {
     CAFFE_CHECK(pd.size() < 2 || !pd[1], this->name() << " cannot backpropagate to label inputs");
+    CAFFE_CHECK(groups_ == 1, this->name() << ": backward through map groups is not supported (inference only)");
     if (!pd.size() || !pd[0] || dx_in_fwd_) return;
     int o, c, i;
     softmax_dims(*bottom[0], axis_, o, c, i);
@@ -810,6 +844,9 @@ class SoftmaxWithLossLayer : public Layer<Dtype> {
   int ignore_ = -1, axis_ = 1;
   bool dx_in_fwd_ = false;
   float *acc_sum_ = nullptr, *acc_row_ = nullptr;  // set_top_accumulator (TEST)
+  int64_t acc_stride_ = 0;
+  int acc_live_ = -1;
+  int groups_ = 1;  // set_map_groups
 };
 
 // --------------------------------------------------------------- Accuracy
@@ -831,13 +868,20 @@ class AccuracyLayer : public Layer<Dtype> {
     softmax_dims(*bottom[0], axis_, o, c, i);
     CAFFE_CHECK(top_k_ <= c, "top_k must be less than or equal to the number of classes");
     CAFFE_CHECK((int64_t)o * i == bottom[1]->count(), "number of labels must match number of predictions");
-    top[0]->Reshape({});
-    counts_.Reshape({2});
+    if (groups_ > 1) top[0]->Reshape({groups_});
+    else top[0]->Reshape({});
+    counts_.Reshape({2 * groups_});
   }
   bool AllowForceBackward(int) const override { return false; }
-  bool set_top_accumulator(float* sum, float* row) override {
+  bool set_top_accumulator(float* sum, float* row, int64_t row_stride = 0, int live = -1) override {
     acc_sum_ = sum;
     acc_row_ = sum ? row : nullptr;
+    acc_stride_ = row_stride;
+    acc_live_ = live;
+    return true;
+  }
+  bool set_map_groups(int K, const Dtype* const*, const int64_t*) override {
+    groups_ = K > 1 ? K : 1;
     return true;
   }
 
@@ -846,6 +890,14 @@ class AccuracyLayer : public Layer<Dtype> {
     int o, c, i;
     softmax_dims(*bottom[0], axis_, o, c, i);
     float* cnt = counts_.mutable_gpu_data();
+    if (groups_ > 1) {
+      CAFFE_CHECK(o % groups_ == 0, this->name() << ": " << o << " rows do not split into " << groups_ << " map groups");
+      RRAM_CALL(rram_accuracy_groups(bottom[0]->gpu_data(), bottom[1]->gpu_data(), cnt, cnt + groups_,
+                                     top[0]->mutable_gpu_data(), groups_, o / groups_, c, i, top_k_, ignore_, acc_sum_,
+                                     acc_row_, acc_stride_, acc_live_ < 0 ? groups_ : std::min(acc_live_, groups_),
+                                     Caffe::stream()));
+      return;
+    }
     RRAM_CALL(rram_accuracy_acc(bottom[0]->gpu_data(), bottom[1]->gpu_data(), cnt, cnt + 1,
                                 top[0]->mutable_gpu_data(), o, c, i, top_k_, ignore_, acc_sum_, acc_row_,
                                 Caffe::stream()));
@@ -855,6 +907,9 @@ class AccuracyLayer : public Layer<Dtype> {
   int top_k_ = 1, axis_ = 1, ignore_ = -1;
   Blob<Dtype> counts_;
   float *acc_sum_ = nullptr, *acc_row_ = nullptr;  // set_top_accumulator
+  int64_t acc_stride_ = 0;
+  int acc_live_ = -1;
+  int groups_ = 1;  // set_map_groups
 };
 
 // ----------------------------------------------------------------- Concat

@@ -47,6 +47,13 @@ class ConvolutionLayer : public Layer<Dtype> {
   // with the flipped kernel (rram_conv2d_flip_applies): its geometry, for
   // the solver's fused update to write that kernel (rram_update_seg.w_flip)
   bool flip_geometry(int* g, int* cin_g, int* cout_g, int* taps) const override;
+  // map groups: per-image work, but the fp32 engine plans its split-K from
+  // num, so the forward pins the plan to one group's batch
+  bool set_map_groups(int K, const Dtype* const*, const int64_t*) override {
+    if (K > 1 && this->phase_ != TEST) return false;
+    groups_ = K > 1 ? K : 1;
+    return true;
+  }
   bool set_octet_reader(Layer<Dtype>* reader) override {
     if (reader != nullptr && (this->phase_ != TEST || concat_top_ != nullptr)) return false;
     octet_reader_ = reader;
@@ -65,6 +72,7 @@ class ConvolutionLayer : public Layer<Dtype> {
   Blob<Dtype>* concat_top_ = nullptr;  // write_into_concat: the output goes to this top at channel concat_off_
   int concat_off_ = 0;
   Layer<Dtype>* octet_reader_ = nullptr;  // convolution-output fold: the top's only reader
+  int groups_ = 1;                        // set_map_groups
   bool flip_ok_ = false;
 };
 
@@ -82,6 +90,16 @@ class InnerProductLayer : public Layer<Dtype> {
   int M() const { return M_; }
   int N() const { return N_; }
   int K() const { return K_; }
+  bool set_map_groups(int K, const Dtype* const* group_params, const int64_t* strides) override {
+    if (K > 1 && this->phase_ != TEST) return false;
+    groups_ = K > 1 ? K : 1;
+    for (int j = 0; j < 2; ++j) {
+      const bool own = groups_ == 1 || group_params == nullptr || j >= (int)this->blobs_.size() || !group_params[j];
+      group_param_[j] = own ? nullptr : group_params[j];
+      group_stride_[j] = own ? 0 : strides[j];
+    }
+    return true;
+  }
 
  protected:
   void Forward_gpu(const std::vector<Blob<Dtype>*>& bottom, const std::vector<Blob<Dtype>*>& top) override;
@@ -92,6 +110,11 @@ class InnerProductLayer : public Layer<Dtype> {
   // split-K partials need up to 16 x M x N floats (<= 256 MB)
   size_t ws_request() const { return std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20); }
   uint64_t in_rows_key_ = 0;  // the packed-row companion this layer reads (Reshape; 0: none)
+  // set_map_groups: the batch rows are groups_ groups of M_ / groups_ rows,
+  // group g reading copy g of a faulted blob (nullptr: the layer's own blob)
+  int groups_ = 1;
+  const Dtype* group_param_[2] = {nullptr, nullptr};
+  int64_t group_stride_[2] = {0, 0};
 };
 
 template <typename Dtype>

@@ -54,6 +54,7 @@ class Net {
   Phase phase() const { return phase_; }
   const std::vector<std::shared_ptr<Layer<Dtype>>>& layers() const { return layers_; }
   const std::vector<std::vector<Blob<Dtype>*>>& top_vecs() const { return top_vecs_; }
+  const std::vector<std::vector<Blob<Dtype>*>>& bottom_vecs() const { return bottom_vecs_; }
   const std::vector<std::string>& layer_names() const { return layer_names_; }
   const std::vector<std::shared_ptr<Blob<Dtype>>>& blobs() const { return blobs_; }
   const std::vector<std::string>& blob_names() const { return blob_names_; }

@@ -1,6 +1,7 @@
 #include "solver.hpp"
 
 #include "hdf5.hpp"
+#include "layers.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -861,6 +862,11 @@ MonteCarlo<Dtype>::~MonteCarlo() {
   }
   drop_graph();
   if (d_state_) (void)hipFree(d_state_);
+  try {
+    apply_map_groups(1);
+  } catch (...) {
+  }
+  for (auto* c : stacks_) (void)hipFree(c);
   for (auto* c : clean_) (void)hipFree(c);
   if (side_) {
     (void)hipStreamSynchronize(side_);
@@ -890,6 +896,8 @@ void MonteCarlo<Dtype>::RestoreClean() {
 
 template <typename Dtype>
 void MonteCarlo<Dtype>::set_reuse_prefix(bool on) {
+  CAFFE_CHECK(!on || map_batch_ == 1, "MonteCarlo prefix reuse: not available while map batching is on (map_batch = "
+                                          << map_batch_ << ")");
   if (on) {
     const auto& L = net_->layers();
     const auto& tops = net_->top_vecs();
@@ -927,6 +935,8 @@ void MonteCarlo<Dtype>::drop_graph() {
 
 template <typename Dtype>
 void MonteCarlo<Dtype>::set_graph(bool on) {
+  CAFFE_CHECK(!on || map_batch_ == 1, "MonteCarlo graph replay: not available while map batching is on (map_batch = "
+                                          << map_batch_ << ")");
   if (on) {
     for (const auto& l : net_->layers())
       CAFFE_CHECK(std::string(l->type()) != "HDF5Data",
@@ -1003,8 +1013,211 @@ void MonteCarlo<Dtype>::map_body(bool dev_state, uint32_t m) {
   }
 }
 
+// ------------------------------------------------------------ map batching
+// hand every layer its group count and, for its faulted blobs, their stacks
+template <typename Dtype>
+void MonteCarlo<Dtype>::apply_map_groups(int K) {
+  const auto& L = net_->layers();
+  std::string refused;
+  for (size_t l = 0; l < L.size(); ++l) {
+    const auto& bl = L[l]->blobs();
+    std::vector<const Dtype*> gp(bl.size() + 1, nullptr);
+    std::vector<int64_t> st(bl.size() + 1, 0);
+    for (size_t j = 0; K > 1 && j < bl.size(); ++j)
+      for (size_t i = 0; i < params_.size(); ++i)
+        if (params_[i] == bl[j].get() || params_[i]->data().get() == bl[j]->data().get()) {
+          gp[j] = stacks_[i];
+          st[j] = params_[i]->count();
+        }
+    const bool ok = L[l]->set_map_groups(K, gp.data(), st.data());
+    const auto& fl = net_->failure_learnable_layer_ids();
+    if (!ok && K > 1 && refused.empty() && std::find(fl.begin(), fl.end(), (int)l) != fl.end())
+      refused = net_->layer_names()[l] + " (" + L[l]->type() + ")";
+  }
+  CAFFE_CHECK(refused.empty(), "MonteCarlo map batching: faultable layer " << refused << " has no map-group forward");
+}
+
+template <typename Dtype>
+void MonteCarlo<Dtype>::set_map_batch(int K) {
+  CAFFE_CHECK(K >= 1, "MonteCarlo map batching: map_batch must be >= 1 (got " << K << ")");
+  if (K == map_batch_) return;
+  // back to the sequential driver first (also the K -> K' path)
+  apply_map_groups(1);
+  map_batch_ = 1;
+  Caffe::synchronize();
+  for (auto* c : stacks_) (void)hipFree(c);
+  stacks_.clear();
+  if (K == 1) return;
+  CAFFE_CHECK(!reuse_prefix_, "MonteCarlo map batching: prefix reuse is on (every map runs its own whole forward; "
+                              "turn it off first)");
+  CAFFE_CHECK(!graph_, "MonteCarlo map batching: graph replay is on (turn it off first)");
+  const auto& L = net_->layers();
+  const auto& tops = net_->top_vecs();
+  const auto& bots = net_->bottom_vecs();
+  for (int l : net_->failure_learnable_layer_ids())
+    CAFFE_CHECK(std::string(L[l]->type()) != "Convolution",
+                "MonteCarlo map batching: a faultable blob belongs to Convolution layer "
+                    << net_->layer_names()[l] << " (the conv-fault extension is not batched)");
+  for (size_t l = 0; l < L.size(); ++l) {
+    if (!bots[l].empty()) continue;
+    CAFFE_CHECK(std::string(L[l]->type()) != "HDF5Data",
+                "MonteCarlo map batching: source layer " << net_->layer_names()[l]
+                                                         << " (HDF5Data) advances between forwards");
+    for (auto* t : tops[l])
+      CAFFE_CHECK(t->num_axes() > 0 && t->shape(0) % K == 0,
+                  "MonteCarlo map batching: the batch " << (t->num_axes() > 0 ? t->shape(0) : 0) << " of source layer "
+                                                        << net_->layer_names()[l] << " is not divisible by map_batch "
+                                                        << K << " (build the net at batch K x B)");
+  }
+  // the producers of the statistics must keep the groups apart
+  for (auto* o : outs_) {
+    int prod = -1;
+    for (size_t l = 0; l < L.size(); ++l)
+      if (!tops[l].empty() && tops[l][0] == o) prod = static_cast<int>(l);
+    CAFFE_CHECK(prod >= 0, "MonteCarlo map batching: an output has no producing layer");
+    const std::string t = L[prod]->type();
+    CAFFE_CHECK(t == "SoftmaxWithLoss" || t == "Accuracy",
+                "MonteCarlo map batching: the statistic of layer " << net_->layer_names()[prod] << " (" << t
+                    << ") mixes the images of a batch, so it cannot be split into map groups");
+  }
+  // batch invariance of the layers before the faultable ones: a convolution
+  // whose plan is chosen from num may sum an image in another order at K * B
+  // than at B.  The fp32 engine's split-K is pinned to the batch-B plan by
+  // the grouped ConvolutionLayer (rram_set_conv_plan_num); the engine choice
+  // and the octet plan must agree, else the K is refused
+  for (size_t l = 0; l < L.size(); ++l) {
+    auto* cv = dynamic_cast<ConvolutionLayer<Dtype>*>(L[l].get());
+    if (cv == nullptr || bots[l].empty() || bots[l][0]->num_axes() != 4) continue;
+    rram_conv_desc big = cv->desc();
+    big.num = bots[l][0]->shape(0);
+    big.height = bots[l][0]->shape(2);
+    big.width = bots[l][0]->shape(3);
+    rram_conv_desc one = big;
+    one.num = big.num / K;
+    bool same = big.num % K == 0 && rram_f32_engine_for_conv(&big) == rram_f32_engine_for_conv(&one);
+    int pb[5] = {0, 0, 0, 0, 0}, po[5] = {0, 0, 0, 0, 0};
+    const int hb = rram_conv_octet_plan(&big, pb), ho = rram_conv_octet_plan(&one, po);
+    same = same && hb == ho && std::equal(pb, pb + 5, po);
+    CAFFE_CHECK(same, "MonteCarlo map batching: convolution " << net_->layer_names()[l] << " takes a different plan at batch "
+                                                              << big.num << " than at " << one.num
+                                                              << ", so map_batch " << K
+                                                              << " would not reproduce the sequential maps' bits");
+  }
+  try {
+    for (auto* p : params_) {
+      Dtype* c = nullptr;
+      const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c), (size_t)K * p->count() * sizeof(Dtype));
+      CAFFE_CHECK(e == hipSuccess, "MonteCarlo map batching: allocating " << K << " copies of a faultable blob ("
+                                                                           << (size_t)K * p->count() * sizeof(Dtype)
+                                                                           << " bytes) failed: " << hipGetErrorString(e));
+      stacks_.push_back(c);
+      // the slices of a short first group are stale but defined: the clean weights
+      for (int j = 0; j < K; ++j)
+        HIP_CALL(hipMemcpyAsync(c + (size_t)j * p->count(), clean_[stacks_.size() - 1], p->count() * sizeof(Dtype),
+                                hipMemcpyDeviceToDevice, Caffe::hip_stream()));
+    }
+    // K spare per-map rows: a group that straddles max_maps writes its rows unclipped
+    const size_t no = std::max<size_t>(outs_.size(), 1);
+    Dtype* rows = nullptr;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&rows), (size_t)(std::max(1, max_maps_) + K) * no * sizeof(Dtype));
+    CAFFE_CHECK(e == hipSuccess, "MonteCarlo map batching: per-map rows allocation failed: " << hipGetErrorString(e));
+    HIP_CALL(hipMemcpyAsync(rows, d_per_map_, (size_t)std::max(1, max_maps_) * no * sizeof(Dtype), hipMemcpyDeviceToDevice,
+                            Caffe::hip_stream()));
+    Caffe::synchronize();
+    (void)hipFree(d_per_map_);
+    d_per_map_ = rows;
+    apply_map_groups(K);
+  } catch (...) {
+    try {
+      apply_map_groups(1);
+    } catch (...) {
+    }
+    (void)hipGetLastError();
+    for (auto* c : stacks_) (void)hipFree(c);
+    stacks_.clear();
+    throw;
+  }
+  map_batch_ = K;
+}
+
+template <typename Dtype>
+void MonteCarlo<Dtype>::TileInputs() {
+  const int K = map_batch_;
+  if (K == 1) return;
+  const auto& tops = net_->top_vecs();
+  const auto& bots = net_->bottom_vecs();
+  for (size_t l = 0; l < tops.size(); ++l) {
+    if (!bots[l].empty()) continue;
+    for (auto* t : tops[l]) {
+      CAFFE_CHECK(t->num_axes() > 0 && t->shape(0) % K == 0, "MonteCarlo TileInputs: batch not divisible by map_batch");
+      const size_t slice = static_cast<size_t>(t->count() / K);
+      Dtype* d = t->mutable_gpu_data();
+      for (int j = 1; j < K; ++j)
+        HIP_CALL(hipMemcpyAsync(d + j * slice, d, slice * sizeof(Dtype), hipMemcpyDeviceToDevice, Caffe::hip_stream()));
+    }
+  }
+}
+
+// Run with map_batch_ > 1: groups of K consecutive map ids, each one
+// rram_inject_rng_maps launch per RRAM_MAX_SEGS blobs, one forward, and the
+// statistics folded by the heads in map order
+template <typename Dtype>
+void MonteCarlo<Dtype>::run_groups(uint32_t map_begin, uint32_t map_count) {
+  const int K = map_batch_;
+  const size_t no = outs_.size();
+  std::vector<Layer<Dtype>*> acc_layers;
+  struct ClearAcc {
+    std::vector<Layer<Dtype>*>& v;
+    ~ClearAcc() {
+      for (auto* a : v) a->set_top_accumulator(nullptr, nullptr);
+    }
+  } clear_acc{acc_layers};
+  {
+    const auto& L = net_->layers();
+    const auto& tops = net_->top_vecs();
+    for (size_t k = 0; k < no; ++k) {
+      Layer<Dtype>* prod = nullptr;
+      for (size_t l = 0; l < L.size(); ++l)
+        if (!tops[l].empty() && tops[l][0] == outs_[k]) prod = L[l].get();
+      CAFFE_CHECK(prod != nullptr && prod->set_top_accumulator(d_sums_ + k, nullptr, (int64_t)no, 0),
+                  "MonteCarlo map batching: an output's producer cannot fold the statistics");
+      acc_layers.push_back(prod);
+    }
+  }
+  std::vector<rram_inject_seg> segs(params_.size());
+  std::vector<int64_t> strides(params_.size());
+  for (size_t i = 0; i < params_.size(); ++i) {
+    segs[i] = rram_inject_seg{clean_[i], stacks_[i], params_[i]->count(), (uint32_t)i, 0, cfgs_[i]};
+    strides[i] = params_[i]->count();
+  }
+  const int prev_grid = rram_set_inject_grid(0);
+  for (uint32_t done = 0; done < map_count; done += K) {
+    const int live = static_cast<int>(std::min<uint32_t>(K, map_count - done));
+    for (size_t k = 0; k < no; ++k)
+      acc_layers[k]->set_top_accumulator(d_sums_ + k,
+                                         maps_run_ < max_maps_ ? d_per_map_ + (size_t)maps_run_ * no + k : nullptr,
+                                         (int64_t)no, live);
+    if (timing_) timer_.start(0, Caffe::hip_stream());
+    for (size_t s = 0; s < segs.size(); s += RRAM_MAX_SEGS) {
+      const int k = static_cast<int>(std::min<size_t>(RRAM_MAX_SEGS, segs.size() - s));
+      RRAM_CALL(rram_inject_rng_maps(segs.data() + s, k, seed_, map_begin + done, live, strides.data() + s,
+                                     d_broken_ + s, Caffe::stream()));
+    }
+    if (timing_) timer_.stop(0, Caffe::hip_stream());
+    net_->Forward(false);
+    maps_run_ += live;
+  }
+  rram_set_inject_grid(prev_grid);
+  if (d_state_)
+    HIP_CALL(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_state_ + 1), maps_run_, 1, Caffe::hip_stream()));
+}
+
 template <typename Dtype>
 void MonteCarlo<Dtype>::Run(uint32_t map_begin, uint32_t map_count) {
+  if (map_batch_ > 1) {
+    run_groups(map_begin, map_count);
+    return;
+  }
   if (graph_ && !reuse_prefix_ && !timing_ && !net_->timing_on() && map_count > 0) {
     GraphStreamScope sc(gstream_);
     hipStream_t st = Caffe::hip_stream();

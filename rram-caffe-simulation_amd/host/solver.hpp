@@ -327,6 +327,35 @@ class MonteCarlo {
   // refuses nets whose source layers advance between forwards (HDF5Data).
   void set_graph(bool on);
   bool graph_active() const { return gexec_ != nullptr; }
+  // Map batching (opt-in; for launch-bound small nets): K fault maps share
+  // every launch of one forward.  The net must have been built at batch K * B:
+  // its batch axis then carries K groups of B images, and map j of a group of
+  // K consecutive map ids evaluates images [j B, (j + 1) B) of the batch with
+  // its own faulted copy of every faultable blob (a driver-owned K-copy stack
+  // per blob, written by one rram_inject_rng_maps launch).  Only the
+  // InnerProduct layers and the loss / accuracy heads know about the groups
+  // (Layer::set_map_groups); the other layers are per-image in TEST phase.
+  // Every map still runs its own whole forward over its own B images, and the
+  // statistics are the sequential driver's bit for bit when the K slices hold
+  // the same B images (TileInputs) -- provided the layers before the first
+  // faultable one give an image the same bits at batch K * B as at B, which
+  // set_map_batch checks for the convolutions' plans and refuses otherwise.
+  // A short last group (count % K maps) injects and folds only its live maps;
+  // its other slices compute on stale weights and are dropped.
+  // Throws, naming the cause, when a source top's num is not divisible by K,
+  // a source advances between forwards (HDF5Data), a statistic's producer
+  // mixes images (EuclideanLoss), a faultable blob is a Convolution's, or
+  // prefix reuse / graph replay is on (their setters throw while K > 1).
+  // RRAM_MC_OVERLAP is ignored while K > 1.  K = 1 undoes all of it.
+  void set_map_batch(int K);
+  int map_batch() const { return map_batch_; }
+  // copy the first B images of every bottom-less layer's tops over the other
+  // K - 1 slices (device to device): every map then sees the same B images
+  void TileInputs();
+  // the K-copy stack of faultable blob i ([K][count]; nullptr while K == 1)
+  const Dtype* map_stack(int i) const { return i >= 0 && i < (int)stacks_.size() ? stacks_[i] : nullptr; }
+  int num_fault_blobs() const { return static_cast<int>(params_.size()); }
+  int64_t fault_blob_count(int i) const { return params_[i]->count(); }
   EventTimer& timer() { return timer_; }
   int64_t fault_weights() const {
     int64_t n = 0;
@@ -365,6 +394,12 @@ class MonteCarlo {
   hipGraphExec_t gexec_ = nullptr;
   GraphStream gstream_;
   std::vector<const void*> graph_ptrs_;  // the device pointers the graph was captured with
+  // map batching: stacks_[i] = K faulted copies of params_[i]; d_per_map_ has
+  // map_batch_ spare rows so a group's rows never need clipping
+  int map_batch_ = 1;
+  std::vector<Dtype*> stacks_;
+  void apply_map_groups(int K);
+  void run_groups(uint32_t map_begin, uint32_t map_count);
   void map_body(bool dev_state, uint32_t m);  // one map's launches on the working stream
   std::vector<const void*> graph_key() const;
   void drop_graph();

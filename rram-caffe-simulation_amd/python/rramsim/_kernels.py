@@ -160,6 +160,12 @@ SIGNATURES = {
     "rram_fill_uniform": (I, [P, I64, F, F, U64, U32, P]),
     "rram_fill_gaussian": (I, [P, I64, F, F, U64, U32, P]),
     "rram_fill_uniform_int": (I, [P, I64, I, F, U64, U32, P]),
+    "rram_set_conv_plan_num": (I, [I]),
+    "rram_inject_rng_maps": (I, [P, I, U64, U32, I, P, P, P]),
+    "rram_ip_fwd_groups": (I, [P, P, I64, P, I64, P, I, I, I, I, I, I, P, SZ, P]),
+    "rram_ip_fwd_groups_fused": (I, [I, I, I, I, I, SZ]),
+    "rram_softmax_loss_fwd_groups": (I, [P, P, P, I, I, I, I, I, P, P, I64, I, P]),
+    "rram_accuracy_groups": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, I64, I, P]),
 }
 
 _lib = None

@@ -54,6 +54,9 @@ SIGNATURES = {
     "rram_mc_set_reuse_prefix": (I, [P, I]),
     "rram_mc_set_graph": (I, [P, I]),
     "rram_mc_graph_active": (I, [P, PI]),
+    "rram_mc_set_map_batch": (I, [P, I]),
+    "rram_mc_tile_inputs": (I, [P]),
+    "rram_mc_map_stack": (I, [P, I, PP, PI64, PI]),
     "rram_mc_inject_times": (I, [P, C.POINTER(C.c_double), C.POINTER(C.c_long), PI64, I]),
     "rram_solver_create": (I, [C.c_char_p, C.c_char_p, C.c_char_p, PP]),
     "rram_solver_destroy": (I, [P]),
@@ -617,7 +620,9 @@ class Solver:
 class MonteCarlo:
     """Fault-map Monte-Carlo inference driver (rram_mc_*)."""
 
-    def __init__(self, net: Net, cfgs, seed: int, max_maps: int = 4096):
+    def __init__(self, net: Net, cfgs, seed: int, max_maps: int = 4096, map_batch: int = 1):
+        """map_batch = K > 1: K fault maps per forward on a net built at batch
+        K x B (set_map_batch)."""
         self._lib = load()
         if not isinstance(cfgs, (list, tuple)):
             cfgs = [cfgs]
@@ -626,6 +631,33 @@ class MonteCarlo:
         check(self._lib.rram_mc_create(net.h, C.cast(arr, C.c_void_p), len(cfgs), seed, max_maps, C.byref(h)),
               "mc_create")
         self.h, self.net, self.max_maps = h, net, max_maps
+        self.map_batch = 1
+        if map_batch != 1:
+            try:
+                self.set_map_batch(map_batch)
+            except Exception:
+                self.close()
+                raise
+
+    def set_map_batch(self, k: int):
+        """Opt-in map batching: K consecutive fault maps share one forward of a
+        net built at batch K x B; map j of a group evaluates images
+        [j B, (j + 1) B) (include/rram_caffe.h rram_mc_set_map_batch).  K = 1
+        restores the sequential driver."""
+        check(self._lib.rram_mc_set_map_batch(self.h, int(k)), "mc_set_map_batch")
+        self.map_batch = int(k)
+
+    def tile_inputs(self):
+        """Copy the first B images of every source top over the other K - 1
+        slices, so every map of a group sees the same images."""
+        check(self._lib.rram_mc_tile_inputs(self.h), "mc_tile_inputs")
+
+    def map_stack(self, i: int):
+        """The K faulted copies of faultable blob i as a [K, count] device
+        tensor (the last group's maps), or None while map_batch == 1."""
+        d, cnt, k = C.c_void_p(), C.c_int64(), C.c_int()
+        check(self._lib.rram_mc_map_stack(self.h, i, C.byref(d), C.byref(cnt), C.byref(k)), "mc_map_stack")
+        return _wrap_device(d.value, (k.value, cnt.value)) if d.value else None
 
     def run(self, begin: int, count: int):
         check(self._lib.rram_mc_run(self.h, begin, count), "mc_run")
@@ -677,7 +709,8 @@ class MonteCarlo:
         std and the normal-approximation confidence half-width z*std/sqrt(n) from
         the per-map records, plus the mean broken cells per faultable blob."""
         st = self.stats()
-        names = [k for k, v in self.net.outputs().items() if v.numel() == 1]
+        # the statistics' outputs: scalars, or one value per map of a group while map batching
+        names = [k for k, v in self.net.outputs().items() if v.numel() == self.map_batch]
         pm = st["per_map"]
         n = len(pm)
         out = {}

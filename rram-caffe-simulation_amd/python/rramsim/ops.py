@@ -412,3 +412,41 @@ def fill_uniform(x, lo, hi, seed, sid=0):
 
 def fill_gaussian(x, mean, std, seed, sid=0):
     K.check(_lib().rram_fill_gaussian(_p(x), x.numel(), mean, std, seed, sid, _stream()), "fill")
+
+
+# ------------------------------------------------------------ map batching
+def inject_maps(segs, seed, map_begin, nmaps, counters_t=None):
+    """segs: list of (w_clean, w_out [nmaps, n], layer_id, cfg): nmaps faulted
+    copies of every segment in one launch (rram_inject_rng_maps)."""
+    arr = (K.InjectSeg * len(segs))()
+    strides = (C.c_int64 * len(segs))()
+    for i, (src, dst, lid, cfg) in enumerate(segs):
+        arr[i] = K.InjectSeg(src.data_ptr(), dst.data_ptr(), src.numel(), lid, 0, cfg)
+        strides[i] = dst.stride(0) if dst.dim() == 2 else src.numel()
+    K.check(_lib().rram_inject_rng_maps(arr, len(segs), seed, map_begin, nmaps, strides, _p(counters_t),
+                                        _stream()), "inject_rng_maps")
+
+
+def ip_fwd_groups(x, w, w_stride, bias, bias_stride, y, G, M, N, K_, transpose=False, relu=False, workspace=None):
+    """G InnerProduct forwards sharing launches (rram_ip_fwd_groups); strides in elements."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_fwd_groups(_p(x), _p(w), w_stride, _p(bias), bias_stride, _p(y), G, M, N, K_,
+                                      int(transpose), int(relu), _p(workspace), wsb, _stream()), "ip_fwd_groups")
+
+
+def ip_fwd_groups_fused(G, M, N, K_, transpose=False, ws_bytes=0):
+    return _lib().rram_ip_fwd_groups_fused(G, M, N, K_, int(transpose), ws_bytes)
+
+
+def softmax_loss_fwd_groups(prob, label, out, G, outer, channels, inner, ignore=-1, acc_sum=None, acc_rows=None,
+                            row_stride=1, live=None):
+    K.check(_lib().rram_softmax_loss_fwd_groups(_p(prob), _p(label), _p(out), G, outer, channels, inner, ignore,
+                                                _p(acc_sum), _p(acc_rows), row_stride, G if live is None else live,
+                                                _stream()), "softmax_loss_fwd_groups")
+
+
+def accuracy_groups(x, label, correct, count, ratio, G, outer, channels, inner, top_k=1, ignore=-1, acc_sum=None,
+                    acc_rows=None, row_stride=1, live=None):
+    K.check(_lib().rram_accuracy_groups(_p(x), _p(label), _p(correct), _p(count), _p(ratio), G, outer, channels,
+                                        inner, top_k, ignore, _p(acc_sum), _p(acc_rows), row_stride,
+                                        G if live is None else live, _stream()), "accuracy_groups")
