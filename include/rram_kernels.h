@@ -396,6 +396,28 @@ int rram_conv_output_octets_only(const rram_conv_desc* d);
  * (0 = tiles run across images), LDS patch pieces per wave.  Returns 1 with
  * the plan filled, 0 when the octet kernel does not take d. */
 int rram_conv_octet_plan(const rram_conv_desc* d, int* plan);
+/* Which forward kernel rram_conv2d_fwd / rram_conv2d_fwd_octets launches for
+ * d (dense y) under the current engine, as text (host only, no device work;
+ * made by the launch paths' own plan functions in their order):
+ *   cb<KH,WR,NB,PD,OCC>/kind        channel-octet kernel, one workgroup per CU
+ *   cb16<KH,WR,NB,PD,OCC;kP>/kind   its 16x16x32 form, two per CU, K-tile parity P
+ *                                   kind = contig | perimg | rowalign | whole
+ *                                   (tiles across images, per image, per image
+ *                                   in whole output rows, whole images)
+ *   c1x1<MI,NB,WR;vV>               1x1 register-ring kernel, V floats per load
+ *   c1x1_dma<MI,NB,WR;vV>           1x1 LDS-DMA kernel
+ *   patch<KH,CPH,MI,PD>             patch kernel
+ *   conv1_ring<227>, conv_s2<NBW>   the two fixed-shape kernels
+ *   f32                             no bf16x6 kernel: the fp32-MFMA implicit GEMM
+ *   none                            num == 0, nothing runs
+ * x_align16: whether x is 16-byte aligned (the 1x1 kernels load 4 floats at a
+ * time only then).  Both calls follow snprintf: they return the text's length
+ * (< 0: an error code) and write at most cap - 1 characters and a NUL;
+ * out = NULL with cap = 0 only measures.
+ * rram_conv_fwd_kernel_list: every instantiated kernel of the above, one id
+ * per line, without the /kind suffix. */
+int rram_conv_fwd_kernel_id(const rram_conv_desc* d, int x_align16, char* out, size_t cap);
+int rram_conv_fwd_kernel_list(char* out, size_t cap);
 /* The fp32 engine's implicit-GEMM forward picks its split-K count from num.
  * num > 0 pins that choice to the plan of a batch of `num` images for every
  * later forward of a larger batch (0: each call's own num, the default), so

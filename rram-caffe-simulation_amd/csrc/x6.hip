@@ -3,9 +3,11 @@
 // gemm.hip's k_conv_patch re-tiled for v_mfma_f32_32x32x16_bf16.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <atomic>
+#include <string>
 #include <type_traits>
 
 #include "gemm_common.hpp"
@@ -2754,6 +2756,9 @@ std::atomic<int>& f32_engine() {
 struct ConvPlan {
   int CPH, MI, mt, PW, CS, PD;
 };
+// instantiated (KH, CPH, PD) combinations of k_conv_patch_x6, each at MI = 3 and 4
+#define RRAM_PATCH_LIST(X) \
+  X(5, 1, 4) X(5, 1, 8) X(5, 1, 12) X(3, 4, 8) X(3, 4, 12) X(3, 4, 16) X(3, 2, 4) X(3, 2, 8) X(3, 2, 16)
 bool conv_x6_plan(const rram_conv_desc* d, ConvPlan& pl) {
   const int KH = d->kernel_h, KW = d->kernel_w;
   if (d->stride_h != 1 || d->stride_w != 1 || d->dilation_h != 1 || d->dilation_w != 1) return false;
@@ -2799,9 +2804,12 @@ int pack_octets(const float* x, void* oct, int num, int C, int HWi, hipStream_t 
 }
 
 // ---- k_conv_cb_x6 (channel-octet pre-split activations) ----
+// how a plan's column tiles lie on the output positions
+enum { CB_CONTIG = 0, CB_PERIMG, CB_ROWALIGN, CB_WHOLE };
 struct CbPlan {
   int WR, NB, RPC, PD, octb, tiles_m, tiles_n, OCC, tpi;
   int tp = 0;  // per-image tiles of tp positions (whole output rows; 0: the tile width)
+  int kind = CB_CONTIG;  // tiling kind (rram_conv_fwd_kernel_id)
 };
 // instantiated (KH, WR, NB, PD, OCC) combinations; OCC = workgroups per CU.
 // One workgroup per CU: k_conv_cb_x6 (32x32x16); two: k_conv_cb16_x6
@@ -2858,6 +2866,7 @@ bool conv_cb_plan_whole_images(const rram_conv_desc* d, CbPlan& pl) {
     if ((int64_t)G * tiles_m * tiles_n >= (1ll << 31)) continue;
     pl = CbPlan{WR, NB, RPC, 8, octb, tiles_m, static_cast<int>(tiles_n), 2, 0};
     pl.tp = tp;
+    pl.kind = CB_WHOLE;
     return true;
   }
   return false;
@@ -2919,6 +2928,7 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
       if (best < 0 || cost < best) {
         best = cost;
         pl = CbPlan{WR, NB, RPC, PD, ob, tiles_m, static_cast<int>(tpi * d->num), 1, tpi};
+        pl.kind = CB_PERIMG;
       }
       continue;
     }
@@ -2994,6 +3004,7 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
           bc = cost;
           pc = CbPlan{WR, NB, RPC, 8, octb, tiles_m, tiles_n, 2, tpi};
           pc.tp = tp;
+          pc.kind = per_image == 2 ? CB_ROWALIGN : per_image == 1 ? CB_PERIMG : CB_CONTIG;
         }
       }
     }
@@ -3181,6 +3192,9 @@ bool conv_1x1_plan(const rram_conv_desc* d, const float* x, C1Plan& pl) {
   return best >= 0;
 }
 
+// the LDS-DMA form of the 1x1 kernel (else the register ring), see conv_1x1_x6_fwd
+bool conv_1x1_dma(const C1Plan& pl, int M) { return pl.VEC == 4 && M > 64; }
+
 int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* y_oct,
                     int relu, hipStream_t s, const WPack& wk) {
   C1Plan pl;
@@ -3228,7 +3242,7 @@ int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, con
   // the DMA form measured faster where the weight panel is tall (M > 64: 4-18 %
   // per layer), the register ring on 16-byte loads with M <= 64 and on the
   // 4-byte loads of the 7 x 7 layers (profiles/r04_ab_conv1x1.txt)
-  const bool dma = pl.VEC == 4 && M > 64;
+  const bool dma = conv_1x1_dma(pl, M);
 #define RRAM_X(mi, nb, wr)                                                                                  \
   if (pl.MI == mi && pl.NB == nb && pl.WR == wr) {                                                          \
     if (dma && pl.VEC == 4)                                                                                 \
@@ -3343,14 +3357,99 @@ int conv_patch_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, c
     rc = MI == 3 ? launch_patch_x6<KH_, CPH_, 3, PD_>(P, wp, PW, CS, G, s)                               \
                  : launch_patch_x6<KH_, CPH_, 4, PD_>(P, wp, PW, CS, G, s);                              \
   else
-  RRAM_P(5, 1, 4) RRAM_P(5, 1, 8) RRAM_P(5, 1, 12)
-  RRAM_P(3, 4, 8) RRAM_P(3, 4, 12) RRAM_P(3, 4, 16)
-  RRAM_P(3, 2, 4) RRAM_P(3, 2, 8) RRAM_P(3, 2, 16)
+  RRAM_PATCH_LIST(RRAM_P)
   return 0;
 #undef RRAM_P
   return rc ? rc : 1;
 }
 
+
+// ---- which forward kernel a descriptor selects (rram_conv_fwd_kernel_id) ----
+// The id of the kernel conv_x6_fwd launches for d with a dense y, from the
+// launch paths' own plans in conv_x6_fwd's order; x_align16 = 0 plans the 1x1
+// kernels for an input that is only 4-byte aligned.
+std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16) {
+  char b[64];
+  if (f32_engine().load(std::memory_order_relaxed) != RRAM_ENGINE_BF16X6) return "f32";
+  const int KH = d->kernel_h;
+  CbPlan cb;
+  if (conv_cb_plan(d, cb) && cb_instantiated(KH, cb.WR, cb.NB, cb.PD, cb.OCC)) {
+    static const char* const kinds[] = {"contig", "perimg", "rowalign", "whole"};
+    if (cb.OCC == 2)
+      snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC,
+               (d->channels / d->group / 16) & 1, kinds[cb.kind]);
+    else
+      snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC, kinds[cb.kind]);
+    return b;
+  }
+  C1Plan c1;
+  // (the plan only looks at the pointer's low bits: 4 = aligned to 4 bytes, not 16)
+  if (conv_1x1_plan(d, x_align16 ? nullptr : reinterpret_cast<const float*>(uintptr_t{4}), c1)) {
+    bool inst = false;
+#define RRAM_X(mi, nb, wr) inst = inst || (c1.MI == mi && c1.NB == nb && c1.WR == wr);
+    RRAM_C1X1_LIST(RRAM_X)
+#undef RRAM_X
+    if (inst) {
+      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>", conv_1x1_dma(c1, d->num_output) ? "c1x1_dma" : "c1x1", c1.MI, c1.NB,
+               c1.WR, c1.VEC);
+      return b;
+    }
+  }
+  if (conv1_ring_ok(d)) return "conv1_ring<227>";
+  if (conv_s2_ok(d)) {
+    snprintf(b, sizeof b, "conv_s2<%d>", RRAM_S2_NBW);
+    return b;
+  }
+  ConvPlan pp;
+  if (conv_x6_plan(d, pp)) {
+    bool inst = false;
+#define RRAM_X(kh, cph, pd) inst = inst || (KH == kh && pp.CPH == cph && pp.PD == pd);
+    RRAM_PATCH_LIST(RRAM_X)
+#undef RRAM_X
+    if (inst) {
+      snprintf(b, sizeof b, "patch<%d,%d,%d,%d>", KH, pp.CPH, pp.MI, pp.PD);
+      return b;
+    }
+  }
+  return "f32";
+}
+
+// every instantiated forward kernel, one id per line (no tiling kind)
+std::string conv_fwd_kernel_list() {
+  std::string out;
+  char b[64];
+#define RRAM_X(kh, wr, nb, pd, occ)                                     \
+  snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>\n", kh, wr, nb, pd, occ); \
+  out += b;
+  RRAM_CB_LIST(RRAM_X)
+#undef RRAM_X
+#define RRAM_X(kh, wr, nb, pd, occ)                                                  \
+  for (int k = 0; k < 2; ++k) {                                                      \
+    snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>\n", kh, wr, nb, pd, occ, k);     \
+    out += b;                                                                        \
+  }
+  RRAM_CB16_LIST(RRAM_X)
+#undef RRAM_X
+#define RRAM_X(mi, nb, wr)                                                            \
+  for (const char* f : {"c1x1", "c1x1_dma"})                                          \
+    for (int v : {4, 1}) {                                                            \
+      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>\n", f, mi, nb, wr, v);                  \
+      out += b;                                                                       \
+    }
+  RRAM_C1X1_LIST(RRAM_X)
+#undef RRAM_X
+#define RRAM_X(kh, cph, pd)                                            \
+  for (int mi : {3, 4}) {                                              \
+    snprintf(b, sizeof b, "patch<%d,%d,%d,%d>\n", kh, cph, mi, pd);    \
+    out += b;                                                          \
+  }
+  RRAM_PATCH_LIST(RRAM_X)
+#undef RRAM_X
+  out += "conv1_ring<227>\n";
+  snprintf(b, sizeof b, "conv_s2<%d>\n", RRAM_S2_NBW);
+  out += b;
+  return out;
+}
 
 // shape plan of the x6 GEMM (false: not covered)
 struct GemmPlan {
@@ -3522,6 +3621,29 @@ int rram_conv_octet_plan(const rram_conv_desc* d, int* plan) {
   plan[4] = cpl.PD;
   return 1;
 }
+
+namespace {
+// snprintf's contract: the text's length, at most cap - 1 characters of it written
+int copy_text(const std::string& t, char* out, size_t cap) {
+  if (out != nullptr && cap > 0) {
+    const size_t n = std::min(t.size(), cap - 1);
+    memcpy(out, t.data(), n);
+    out[n] = 0;
+  }
+  return static_cast<int>(t.size());
+}
+}  // namespace
+
+int rram_conv_fwd_kernel_id(const rram_conv_desc* d_in, int x_align16, char* out, size_t cap) {
+  RRAM_REQUIRE(d_in != nullptr, "kernel id query: desc is NULL");
+  rram_conv_desc d = *d_in;
+  const int rc = rram_conv_out_shape(&d);
+  if (rc) return rc;
+  RRAM_REQUIRE((int64_t)d.num * d.out_h * d.out_w < (1ll << 31), "kernel id query: too many output positions");
+  return copy_text(d.num == 0 ? std::string("none") : rram::conv_fwd_kernel_id(&d, x_align16 != 0), out, cap);
+}
+
+int rram_conv_fwd_kernel_list(char* out, size_t cap) { return copy_text(rram::conv_fwd_kernel_list(), out, cap); }
 
 int rram_conv_output_octets_only(const rram_conv_desc* d_in) {
   RRAM_REQUIRE(d_in != nullptr, "output octets query: desc is NULL");

@@ -113,6 +113,8 @@ SIGNATURES = {
     "rram_conv2d_fwd_octets": (I, [P, P, P, P, P, P, P, I, P]),
     "rram_conv_input_octets": (I, [P]),
     "rram_conv_octet_plan": (I, [P, P]),
+    "rram_conv_fwd_kernel_id": (I, [P, I, C.c_char_p, SZ]),
+    "rram_conv_fwd_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_conv_weight_pack_bytes": (SZ, [P]),
     "rram_conv2d_fwd_cached": (I, [P, P, P, P, P, I, P, P, P, I, P]),
     "rram_conv2d_fwd_strided": (I, [P, P, P, P, P, I, P, P, C.c_int64, I, P]),

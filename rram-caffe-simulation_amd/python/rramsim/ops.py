@@ -253,6 +253,25 @@ def conv_octet_plan(d):
     return dict(rows=plan[0], cols=plan[1], per_cu=plan[2], tiles_per_image=plan[3], pieces=plan[4])
 
 
+def conv_fwd_kernel_id(d, x_align16=True):
+    """Text id of the forward kernel conv2d_fwd / conv2d_fwd_octets would
+    launch for d now (rram_conv_fwd_kernel_id; host only): e.g.
+    'cb16<3,2,2,8,2;k1>/rowalign', 'c1x1_dma<4,2,1;v4>', 'patch<3,4,3,8>', 'f32'."""
+    buf = C.create_string_buffer(96)
+    n = _lib().rram_conv_fwd_kernel_id(C.byref(d), int(bool(x_align16)), buf, len(buf))
+    if n < 0:
+        K.check(n, "conv_fwd_kernel_id")
+    return buf.value.decode()
+
+
+def conv_fwd_kernel_list():
+    """Ids of every instantiated bf16x6 forward kernel (no tiling-kind suffix)."""
+    n = _lib().rram_conv_fwd_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_conv_fwd_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
 def pack_octets(x, oct_, n, c, h, w):
     K.check(_lib().rram_pack_octets(_p(x), _p(oct_), n, c, h, w, _stream()), "pack_octets")
 

@@ -19,16 +19,15 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, rdv, q):
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     sys.path.insert(0, str(root / "rram-caffe-simulation_amd" / "python"))
     import torch
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world)
     from rramsim import models
     from rramsim.parallel import DataParallelSolver
     sp = models.solver(base_lr=0.01, momentum=0.9, weight_decay=0.0005, max_iter=10,
@@ -47,17 +46,8 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_stay_identical(device):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted(q.get(timeout=300) for _ in ps)
-    for p in ps:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    from _ranks import run_ranks
+    res = sorted(run_ranks(_worker, 2, lambda r, rdv, q: (r, 2, rdv, q)))
     (_, w0, ww0, e0, n0, d0, b0), (_, w1, ww1, e1, n1, d1, b1) = res
     assert n0 == n1 == 3                       # one gradient all-reduce per iteration
     assert d0 != d1                            # different data shards per rank
@@ -65,16 +55,15 @@ def test_two_ranks_stay_identical(device):
     assert e0 == e1 and b0 == b1               # identical fault state
 
 
-def _equiv_worker(rank, world, port, q, data, label, overlap):
+def _equiv_worker(rank, world, rdv, q, data, label, overlap):
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     sys.path.insert(0, str(root / "rram-caffe-simulation_amd" / "python"))
     import torch
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world)
     from rramsim import models
     from rramsim.parallel import DataParallelSolver
     dp = DataParallelSolver(_equiv_solver(), models.lenet(train_batch=32, test_batch=32),
@@ -100,18 +89,9 @@ def _equiv_solver():
 
 
 def _run_equiv(data, label, overlap):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_equiv_worker, args=(r, 2, port, q, data, label, overlap)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted((q.get(timeout=300) for _ in ps), key=lambda t: t[0])
-    for p in ps:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return res
+    from _ranks import run_ranks
+    return sorted(run_ranks(_equiv_worker, 2, lambda r, rdv, q: (r, 2, rdv, q, data, label, overlap)),
+                  key=lambda t: t[0])
 
 
 def test_dp_two_ranks_equal_one_process_double_batch(device):

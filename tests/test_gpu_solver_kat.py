@@ -26,8 +26,6 @@ arithmetic the reference itself ships.  The analytic update is evaluated in
 float64 (the reference evaluates the same formula in Dtype loops; the 1e-2
 tolerance covers either).
 """
-import os
-import socket
 from pathlib import Path
 
 import numpy as np
@@ -252,31 +250,22 @@ def test_snapshot(device, tmp_path, share):                            # :674-69
 
 
 # ------------------------------------------------ multi-device (:456-486)
-def _free_port():
-    sk = socket.socket()
-    sk.bind(("127.0.0.1", 0))
-    p = sk.getsockname()[1]
-    sk.close()
-    return p
-
-
-def _dp_worker(rank, world, port, backend, list_file, cases, q, shard=False):
+def _dp_worker(rank, world, rdv, backend, list_file, cases, q, shard=False):
     import sys
     sys.path.insert(0, str(ROOT / "rram-caffe-simulation_amd" / "python"))
     import torch
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     comm = None
     if backend == "nccl":
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        dist.init_process_group("nccl", init_method=rdv, rank=rank, world_size=world, device_id=dev)
     elif backend == "native":      # the C++ host's RCCL communicator; gloo only hands out its id
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world)
         from rramsim import caffe
         comm = caffe.Comm(rank, world)
     else:
-        dist.init_process_group(backend, rank=rank, world_size=world)
+        dist.init_process_group(backend, init_method=rdv, rank=rank, world_size=world)
     from rramsim.parallel import DataParallelSolver
     out = []
     for lr, wd, mom, iters in cases:
@@ -297,19 +286,9 @@ def _dp_worker(rank, world, port, backend, list_file, cases, q, shard=False):
 
 
 def _run_dp(world, backend, list_file, cases, shard=False):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_dp_worker, args=(r, world, port, backend, list_file, cases, q, shard))
-          for r in range(world)]
-    for p in ps:
-        p.start()
-    res = sorted((q.get(timeout=300) for _ in ps), key=lambda t: t[0])
-    for p in ps:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return res
+    from _ranks import run_ranks
+    return sorted(run_ranks(_dp_worker, world, lambda r, rdv, q: (r, world, rdv, backend, list_file, cases, q, shard)),
+                  key=lambda t: t[0])
 
 
 def _multi_device_expected(tmp_path, cases, devices):

@@ -1,26 +1,16 @@
 """CPU tests of the multi-process path with the gloo backend (world_size 2):
 map sharding, gradient averaging (the RCCL all-reduce's arithmetic) and the
 statistics all-reduce used by bench.py / the Monte-Carlo driver."""
-import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import run_ranks
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, rdv, q):
+    dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world)
     from rramsim.parallel import allreduce_stats, average_gradients, shard_maps
     g = torch.full((1000,), float(rank + 1))
     average_gradients(g, world)
@@ -32,16 +22,7 @@ def _worker(rank, world, port, q):
 
 
 def test_gloo_world2_gradient_average_and_stats():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in ps)
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = sorted(run_ranks(_worker, 2, lambda r, rdv, q: (r, 2, rdv, q), timeout=120, join_timeout=60))
     assert res[0][1] == res[1][1] == 1.5                 # (1 + 2) / 2
     assert res[0][2] == res[1][2] == [2.0, 4.0]          # (0.5 + 1.5), (2 + 2)
     assert res[0][3] == [0, 2, 4, 6, 8] and res[1][3] == [1, 3, 5, 7, 9]
@@ -87,9 +68,8 @@ def test_plan_buckets_suffixes_in_backward_order():
     assert p2 == {4: (25570, total)}                       # [0, 25570) is the gradients-ready remainder
 
 
-def _bucket_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _bucket_worker(rank, world, rdv, q):
+    dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world)
     from rramsim.parallel import average_gradients, plan_buckets
     g = torch.arange(10_000, dtype=torch.float32) * (rank + 1) / 7.0
     ref = g.clone()
@@ -113,16 +93,7 @@ def _bucket_worker(rank, world, port, q):
 
 
 def test_gloo_world2_bucketed_allreduce_equals_flat():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in ps)
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = sorted(run_ranks(_bucket_worker, 2, lambda r, rdv, q: (r, 2, rdv, q), timeout=120, join_timeout=60))
     assert res[0][1] and res[1][1]
     assert res[0][2] == [(1, (0, 3000)), (3, (3000, 10_000))]
 
