@@ -169,8 +169,14 @@ int rram_solver_num_fail_blobs(rram_solver_t s, int* n);
 int rram_solver_fail_state(rram_solver_t s, int i, float** endurance, float** values, int64_t* count);
 /* broken cells per faultable blob after the last Fail() (device count, one D2H) */
 int rram_solver_broken_counts(rram_solver_t s, unsigned long long* out, int cap, int* n);
-/* SGDSolver::history() (sgd_solver.hpp:29, sgd_solver.cpp:16-26): the momentum
- * history blob of learnable param i (device pointer, count). */
+/* Solver::type() (sgd_solvers.hpp): "SGD", "Nesterov", "AdaGrad", "RMSProp",
+ * "AdaDelta" or "Adam", from the prototxt's `type` or its deprecated
+ * `solver_type` enum (caffe.proto:233-242); NUL-terminated, cut at cap. */
+int rram_solver_type(rram_solver_t s, char* out, int cap);
+/* SGDSolver::history() (sgd_solver.hpp:29, sgd_solver.cpp:16-26): history
+ * blob i (device pointer, count).  One per learnable param; AdaDelta and Adam
+ * keep 2 * nparams, blob i + nparams being the second history of param i
+ * (adadelta_solver.cpp:8-16, adam_solver.cpp:8-17). */
 int rram_solver_num_history(rram_solver_t s, int* n);
 int rram_solver_history(rram_solver_t s, int i, float** data, int64_t* count);
 

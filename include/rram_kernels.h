@@ -264,6 +264,80 @@ typedef struct rram_update_seg {
 int rram_fused_update_fail_batched(const rram_update_seg* segs, int nsegs, float momentum,
                                    float decrement, float eps, rram_stream_t stream);
 
+/* The other five solver types' update kernels.  Each evaluates its reference
+ * kernel's expression literally in fp32, left to right, every product and sum
+ * rounded on its own (no FMA contraction), IEEE sqrt and divide; 1 - momentum,
+ * 1 + momentum and 1 - rms_decay are formed in fp32.
+ *   Nesterov (src/caffe/solvers/nesterov_solver.cu:7-14):
+ *     hn = h = momentum*h + local_rate*g;  g = (1 + momentum)*hn - momentum*h_old
+ *   AdaGrad  (adagrad_solver.cu:7-14):
+ *     h = h + g*g;  g = local_rate*g / (sqrt(h) + delta)
+ *   RMSProp  (rmsprop_solver.cu:7-14):
+ *     h = rms_decay*h + (1 - rms_decay)*g*g;  g = local_rate*g / (sqrt(h) + delta)
+ *   AdaDelta (adadelta_solver.cu:7-16):
+ *     h = momentum*h + (1 - momentum)*g*g;  u = g * sqrt((h2 + delta) / (h + delta));
+ *     h2 = momentum*h2 + (1 - momentum)*u*u;  g = local_rate*u
+ *   Adam     (adam_solver.cu:7-15):
+ *     m = m*beta1 + g*(1 - beta1);  v = v*beta2 + g*g*(1 - beta2);
+ *     g = corrected_local_rate*m / (sqrt(v) + eps_hat) */
+int rram_nesterov_update(float* g, float* h, int64_t n, float momentum, float local_rate,
+                         rram_stream_t stream);
+int rram_adagrad_update(float* g, float* h, int64_t n, float delta, float local_rate,
+                        rram_stream_t stream);
+int rram_rmsprop_update(float* g, float* h, int64_t n, float rms_decay, float delta,
+                        float local_rate, rram_stream_t stream);
+int rram_adadelta_update(float* g, float* h, float* h2, int64_t n, float momentum, float delta,
+                         float local_rate, rram_stream_t stream);
+int rram_adam_update(float* g, float* m, float* v, int64_t n, float beta1, float beta2,
+                     float eps_hat, float corrected_local_rate, rram_stream_t stream);
+
+/* The fused training tail for any solver type.  Per element, in the
+ * reference's order (sgd_solver.cpp:101-116, solver.cpp:299-305):
+ *   g += decay * w; g = <the type's update>(g, h, h2); if (|g| <= thr) g = 0;
+ *   w -= g; FailKernel(e, v, w, g); the optional w_flip write.
+ * RRAM_SOLVER_SGD computes what rram_fused_update_fail_batched computes. */
+enum {
+  RRAM_SOLVER_SGD = 0,
+  RRAM_SOLVER_NESTEROV = 1,
+  RRAM_SOLVER_ADAGRAD = 2,
+  RRAM_SOLVER_RMSPROP = 3,
+  RRAM_SOLVER_ADADELTA = 4,
+  RRAM_SOLVER_ADAM = 5
+};
+/* solver-wide scalars (SolverParameter's fields of the same names) */
+typedef struct rram_solver_hyper {
+  float momentum;  /* SGD, Nesterov, AdaDelta: momentum; Adam: beta1 */
+  float momentum2; /* Adam: beta2 (momentum2); RMSProp: rms_decay */
+  float delta;     /* AdaGrad, RMSProp, AdaDelta: delta; Adam: eps_hat */
+} rram_solver_hyper;
+/* rram_update_seg plus the second history (AdaDelta's squared-update
+ * history, Adam's v): NULL for the one-history types.  local_rate is the
+ * rate the type's kernel takes: for Adam it carries the bias correction. */
+typedef struct rram_opt_seg {
+  float* w;
+  float* g;
+  float* h;
+  float* endurance;     /* NULL for a non-faultable blob */
+  const float* values;  /* NULL iff endurance is NULL */
+  int64_t n;
+  float decay, local_rate, thr;
+  int apply_thr;
+  unsigned long long* broken_count; /* may be NULL */
+  float* w_flip;                    /* as rram_update_seg.w_flip */
+  int flip_groups, flip_cin, flip_cout, flip_taps;
+  float* h2;
+} rram_opt_seg;
+int rram_fused_opt_update_fail(float* w, float* g, float* h, float* h2, float* endurance,
+                               const float* values, int64_t n, int kind,
+                               const rram_solver_hyper* hyper, float decay, float local_rate,
+                               int apply_thr, float thr, float decrement, float eps,
+                               unsigned long long* broken_count, rram_stream_t stream);
+/* One launch for up to RRAM_MAX_SEGS blobs; bit-identical to nsegs calls of
+ * rram_fused_opt_update_fail; broken_count may repeat across segments. */
+int rram_fused_opt_update_fail_batched(const rram_opt_seg* segs, int nsegs, int kind,
+                                       const rram_solver_hyper* hyper, float decrement, float eps,
+                                       rram_stream_t stream);
+
 /* Level-1 helpers used by Blob::Update, Regularize, P2PSync-equivalent
  * scaling (src/caffe/util/math_functions.cu:45-207). */
 int rram_axpy(int64_t n, float alpha, const float* x, float* y, rram_stream_t stream);

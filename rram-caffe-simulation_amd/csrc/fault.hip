@@ -617,6 +617,139 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------------------
+// The five non-SGD solver types (src/caffe/solvers/*_solver.cu): the .cu
+// files' expressions, literally, in fp32, left to right, every product and sum
+// rounded on its own.  a = momentum / beta1 (rms_decay for RMSProp),
+// b = momentum2 / beta2, h2 only for AdaDelta and Adam.  Returns the update
+// value (the new g[i]); h and h2 are the element's histories, in and out.
+// ---------------------------------------------------------------------------
+template <int KIND>
+__device__ __forceinline__ float opt_update(float gi, float& h, float& h2, float a, float b, float delta,
+                                            float lr) {
+#pragma clang fp contract(off)
+  if (KIND == RRAM_SOLVER_SGD) {  // sgd_solver.cu:6-12 (k_sgd_update)
+    const float v = a * h + lr * gi;
+    h = v;
+    return v;
+  } else if (KIND == RRAM_SOLVER_NESTEROV) {  // nesterov_solver.cu:7-14
+    const float hi = h;
+    const float hn = a * hi + lr * gi;
+    h = hn;
+    return (1.0f + a) * hn - a * hi;
+  } else if (KIND == RRAM_SOLVER_ADAGRAD) {  // adagrad_solver.cu:7-14
+    const float hi = h + gi * gi;
+    h = hi;
+    return lr * gi / (sqrtf(hi) + delta);
+  } else if (KIND == RRAM_SOLVER_RMSPROP) {  // rmsprop_solver.cu:7-14
+    const float hi = a * h + (1.0f - a) * gi * gi;
+    h = hi;
+    return lr * gi / (sqrtf(hi) + delta);
+  } else if (KIND == RRAM_SOLVER_ADADELTA) {  // adadelta_solver.cu:7-16
+    const float hi = a * h + (1.0f - a) * gi * gi;
+    h = hi;
+    const float u = gi * sqrtf((h2 + delta) / (hi + delta));
+    h2 = a * h2 + (1.0f - a) * u * u;
+    return lr * u;
+  } else {  // RRAM_SOLVER_ADAM, adam_solver.cu:7-15 (lr: the corrected local rate)
+    const float mi = h * a + gi * (1.0f - a);
+    h = mi;
+    const float vi = h2 * b + gi * gi * (1.0f - b);
+    h2 = vi;
+    return lr * mi / (sqrtf(vi) + delta);
+  }
+}
+
+constexpr bool opt_two_histories(int kind) { return kind == RRAM_SOLVER_ADADELTA || kind == RRAM_SOLVER_ADAM; }
+
+template <int KIND>
+__global__ void __launch_bounds__(256)
+    k_opt_update(float* __restrict__ g, float* __restrict__ h, float* __restrict__ h2, int64_t n, float a, float b,
+                 float delta, float lr) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float hi = h[i];
+    float h2i = 0.0f;
+    if (opt_two_histories(KIND)) h2i = h2[i];
+    g[i] = opt_update<KIND>(g[i], hi, h2i, a, b, delta, lr);
+    h[i] = hi;
+    if (opt_two_histories(KIND)) h2[i] = h2i;
+  }
+}
+
+// k_fused_update_fail_batched for any solver type: the same dealing of
+// kUpdChunk block-chunks across the segments and the same per-element order
+// (decay, the type's update, threshold, w -= g, Fail, flipped kernel), the
+// type a template parameter.  A pure stream: 9 floats per faultable element
+// for the one-history types (w g h e in and out, v in), 11 with h2.
+struct OptSegs {
+  rram_opt_seg s[RRAM_MAX_SEGS];
+  int64_t chunk_start[RRAM_MAX_SEGS + 1];
+  int nsegs;
+};
+
+template <int KIND>
+__global__ void __launch_bounds__(256)
+    k_fused_opt_update_fail_batched(OptSegs segs, float a, float b, float delta, float dec, float eps) {
+#pragma clang fp contract(off)
+  const int64_t total = segs.chunk_start[segs.nsegs];
+  int cur = -1;  // block-uniform: flush the count once per segment visited
+  unsigned cnt = 0;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    int s = 0;
+    while (c >= segs.chunk_start[s + 1]) ++s;
+    if (s != cur) {
+      if (cur >= 0) block_count_flush(cnt, segs.s[cur].broken_count);
+      cnt = 0;
+      cur = s;
+    }
+    const rram_opt_seg& sg = segs.s[s];
+    const int64_t begin = (c - segs.chunk_start[s]) * kUpdChunk;
+    const int64_t end = min(begin + (int64_t)kUpdChunk, sg.n);
+    float* __restrict__ w = sg.w;
+    float* __restrict__ g = sg.g;
+    float* __restrict__ h = sg.h;
+    float* __restrict__ h2 = sg.h2;
+    float* __restrict__ e = sg.endurance;
+    const float* __restrict__ v = sg.values;
+    for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+      float wi = w[i];
+      float gi = g[i];
+      float hi = h[i];
+      float h2i = 0.0f;
+      if (opt_two_histories(KIND)) h2i = h2[i];
+      if (sg.decay != 0.0f) gi = sg.decay * wi + gi;
+      gi = opt_update<KIND>(gi, hi, h2i, a, b, delta, sg.local_rate);
+      h[i] = hi;
+      if (opt_two_histories(KIND)) h2[i] = h2i;
+      if (sg.apply_thr && fabsf(gi) <= sg.thr) gi = 0.0f;
+      g[i] = gi;
+      wi = wi - gi;
+      if (e != nullptr) {
+        float ee = e[i];
+        bool wr;
+        float wv;
+        cnt += fail_one(gi, wv, ee, v[i], dec, eps, wr);
+        e[i] = ee;
+        if (wr) wi = wv;
+      }
+      w[i] = wi;
+      if (sg.w_flip != nullptr) {  // (the host checked G cin cout taps == n < 2^31)
+        const int T = sg.flip_taps, ci = sg.flip_cin, co = sg.flip_cout;
+        int t = static_cast<int>(i);
+        const int tap = t % T;
+        t /= T;
+        const int c = t % ci;
+        t /= ci;
+        const int o = t % co;
+        const int gr = t / co;
+        sg.w_flip[((gr * ci + c) * co + o) * T + (T - 1 - tap)] = wi;
+      }
+    }
+  }
+  if (cur >= 0) block_count_flush(cnt, segs.s[cur].broken_count);
+}
+
+// ---------------------------------------------------------------------------
 // level-1 helpers
 // ---------------------------------------------------------------------------
 __global__ void k_axpby(int64_t n, float a, const float* __restrict__ x, float b,
@@ -989,6 +1122,18 @@ int inject_batched_core(const rram_inject_seg* segs, int nsegs, uint64_t seed, u
 }  // namespace
 }  // namespace rram
 
+template <int KIND>
+static int launch_opt_update(const char* what, float* g, float* h, float* h2, int64_t n, float a, float b, float delta,
+                      float lr, rram_stream_t s) {
+  using namespace rram;
+  RRAM_REQUIRE(n >= 0, "%s: n < 0", what);
+  if (n == 0) return RRAM_OK;
+  RRAM_REQUIRE(g && h && (h2 || !opt_two_histories(KIND)), "%s: NULL pointer", what);
+  hipLaunchKernelGGL(k_opt_update<KIND>, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), g, h, h2, n, a, b,
+                     delta, lr);
+  return launch_status(what);
+}
+
 extern "C" {
 
 int rram_inject_rng(const float* w_clean, float* w_out, int64_t n, const rram_inject_cfg* cfg,
@@ -1079,6 +1224,98 @@ int rram_fused_update_fail_batched(const rram_update_seg* segs, int nsegs, float
   const int grid = static_cast<int>(total < 2048 ? total : 2048);
   hipLaunchKernelGGL(k_fused_update_fail_batched, dim3(grid), dim3(kThreads), 0, as_stream(s), us, mom, dec, eps);
   return launch_status("fused_update_fail_batched");
+}
+
+int rram_nesterov_update(float* g, float* h, int64_t n, float momentum, float local_rate, rram_stream_t s) {
+  return launch_opt_update<RRAM_SOLVER_NESTEROV>("nesterov_update", g, h, nullptr, n, momentum, 0.0f, 0.0f, local_rate,
+                                                 s);
+}
+int rram_adagrad_update(float* g, float* h, int64_t n, float delta, float local_rate, rram_stream_t s) {
+  return launch_opt_update<RRAM_SOLVER_ADAGRAD>("adagrad_update", g, h, nullptr, n, 0.0f, 0.0f, delta, local_rate, s);
+}
+int rram_rmsprop_update(float* g, float* h, int64_t n, float rms_decay, float delta, float local_rate,
+                        rram_stream_t s) {
+  return launch_opt_update<RRAM_SOLVER_RMSPROP>("rmsprop_update", g, h, nullptr, n, rms_decay, 0.0f, delta, local_rate,
+                                                s);
+}
+int rram_adadelta_update(float* g, float* h, float* h2, int64_t n, float momentum, float delta, float local_rate,
+                         rram_stream_t s) {
+  return launch_opt_update<RRAM_SOLVER_ADADELTA>("adadelta_update", g, h, h2, n, momentum, 0.0f, delta, local_rate, s);
+}
+int rram_adam_update(float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps_hat,
+                     float corrected_local_rate, rram_stream_t s) {
+  return launch_opt_update<RRAM_SOLVER_ADAM>("adam_update", g, m, v, n, beta1, beta2, eps_hat, corrected_local_rate,
+                                             s);
+}
+
+int rram_fused_opt_update_fail_batched(const rram_opt_seg* segs, int nsegs, int kind, const rram_solver_hyper* hyper,
+                                       float dec, float eps, rram_stream_t s) {
+  using namespace rram;
+  RRAM_REQUIRE(nsegs >= 0 && nsegs <= RRAM_MAX_SEGS, "fused_opt_update_fail_batched: nsegs out of range");
+  RRAM_REQUIRE(kind >= RRAM_SOLVER_SGD && kind <= RRAM_SOLVER_ADAM, "fused_opt_update_fail_batched: solver kind %d",
+               kind);
+  RRAM_REQUIRE(hyper, "fused_opt_update_fail_batched: hyper is NULL");
+  if (nsegs == 0) return RRAM_OK;
+  RRAM_REQUIRE(segs, "fused_opt_update_fail_batched: segs is NULL");
+  OptSegs us{};
+  us.nsegs = nsegs;
+  for (int i = 0; i < nsegs; ++i) {
+    const rram_opt_seg& sg = segs[i];
+    RRAM_REQUIRE(sg.n >= 0, "fused_opt_update_fail_batched: segment %d n < 0", i);
+    if (sg.n > 0) RRAM_REQUIRE(sg.w && sg.g && sg.h, "fused_opt_update_fail_batched: segment %d NULL pointer", i);
+    if (sg.n > 0 && opt_two_histories(kind))
+      RRAM_REQUIRE(sg.h2, "fused_opt_update_fail_batched: segment %d h2 is NULL (AdaDelta and Adam keep two histories)",
+                   i);
+    RRAM_REQUIRE((sg.endurance == nullptr) == (sg.values == nullptr),
+                 "fused_opt_update_fail_batched: segment %d endurance/values mismatch", i);
+    if (sg.w_flip != nullptr)
+      RRAM_REQUIRE(sg.flip_groups > 0 && sg.flip_cin > 0 && sg.flip_cout > 0 && sg.flip_taps > 0 &&
+                       (int64_t)sg.flip_groups * sg.flip_cin * sg.flip_cout * sg.flip_taps == sg.n && sg.n < (1ll << 31),
+                   "fused_opt_update_fail_batched: segment %d flip geometry %d x %d x %d x %d != n %lld", i,
+                   sg.flip_groups, sg.flip_cin, sg.flip_cout, sg.flip_taps, (long long)sg.n);
+    us.s[i] = sg;
+    us.chunk_start[i + 1] = us.chunk_start[i] + (sg.n + kUpdChunk - 1) / kUpdChunk;
+  }
+  const int64_t total = us.chunk_start[nsegs];
+  if (total == 0) return RRAM_OK;
+  const int grid = static_cast<int>(total < 2048 ? total : 2048);
+  // a: momentum / beta1, the decay rate of RMSProp's one history
+  const float a = kind == RRAM_SOLVER_RMSPROP ? hyper->momentum2 : hyper->momentum;
+  const float b = hyper->momentum2, delta = hyper->delta;
+#define RRAM_OPT_LAUNCH(K)                                                                                          \
+  case K:                                                                                                           \
+    hipLaunchKernelGGL(k_fused_opt_update_fail_batched<K>, dim3(grid), dim3(kThreads), 0, as_stream(s), us, a, b, \
+                       delta, dec, eps);                                                                            \
+    break;
+  switch (kind) {
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_SGD)
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_NESTEROV)
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADAGRAD)
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_RMSPROP)
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADADELTA)
+    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADAM)
+  }
+#undef RRAM_OPT_LAUNCH
+  return launch_status("fused_opt_update_fail_batched");
+}
+
+int rram_fused_opt_update_fail(float* w, float* g, float* h, float* h2, float* e, const float* v, int64_t n, int kind,
+                               const rram_solver_hyper* hyper, float decay, float local_rate, int apply_thr, float thr,
+                               float dec, float eps, unsigned long long* counter, rram_stream_t s) {
+  rram_opt_seg sg{};
+  sg.w = w;
+  sg.g = g;
+  sg.h = h;
+  sg.endurance = e;
+  sg.values = v;
+  sg.n = n;
+  sg.decay = decay;
+  sg.local_rate = local_rate;
+  sg.thr = thr;
+  sg.apply_thr = apply_thr;
+  sg.broken_count = counter;
+  sg.h2 = h2;
+  return rram_fused_opt_update_fail_batched(&sg, 1, kind, hyper, dec, eps, s);
 }
 
 int rram_axpy(int64_t n, float a, const float* x, float* y, rram_stream_t s) {

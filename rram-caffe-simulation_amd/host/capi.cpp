@@ -477,6 +477,12 @@ int rram_solver_smoothed_loss(rram_solver_t s, float* l) {
     *l = s->solver->smoothed_loss();
   });
 }
+int rram_solver_type(rram_solver_t s, char* out, int cap) {
+  return guarded([&] {
+    NEED(s);
+    copy_str(s->solver->type(), out, cap);
+  });
+}
 int rram_solver_learning_rate(rram_solver_t s, float* lr) {
   return guarded([&] {
     NEED(s);

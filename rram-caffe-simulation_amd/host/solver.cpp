@@ -190,6 +190,7 @@ Solver<Dtype>::Solver(const Msg& sp, const Msg* net_param, const Msg& options) :
     Caffe::set_random_seed(static_cast<uint64_t>(sp.integer("random_seed")));
   fused_update_ = options.boolean("fused_update", false);
   flip_cache_ = options.boolean("conv_flip_cache", true);
+  InitSolverType();
   const Msg np = load_net_param(sp, net_param);
   net_ = std::make_shared<Net<Dtype>>(np, TRAIN, options);
   // solver.cpp:132-148: fault maker and strategies on the root solver
@@ -212,8 +213,13 @@ Solver<Dtype>::Solver(const Msg& sp, const Msg* net_param, const Msg& options) :
     HIP_CALL(hipMemsetAsync(history_.back()->mutable_gpu_data(), 0, p->count() * sizeof(Dtype), Caffe::hip_stream()));
     temp_.push_back(std::make_unique<Blob<Dtype>>(p->shape()));
   }
-  CAFFE_CHECK(param_.str("type", "SGD") == "SGD" && param_.str("solver_type", "SGD") == "SGD",
-              "only the SGD solver is part of this build (SURVEY.md §2.1)");
+  // AdaDelta and Adam keep a second set of histories after the first
+  // (adadelta_solver.cpp:8-16, adam_solver.cpp:8-17): history_[i + nparams]
+  if (kind_ == RRAM_SOLVER_ADADELTA || kind_ == RRAM_SOLVER_ADAM)
+    for (auto* p : net_->learnable_params()) {
+      history_.push_back(std::make_unique<Blob<Dtype>>(p->shape()));
+      HIP_CALL(hipMemsetAsync(history_.back()->mutable_gpu_data(), 0, p->count() * sizeof(Dtype), Caffe::hip_stream()));
+    }
   const int64_t nflat = net_->flat_param_count();
   if (nflat > 0 && options.boolean("flat_params", true)) {
     HIP_CALL(hipMalloc(&flat_, 2 * nflat * sizeof(Dtype)));
@@ -314,13 +320,103 @@ void Solver<Dtype>::Regularize(int id) {
   }
 }
 
-// sgd_solver.cpp:216-247 (GPU branch: SGDUpdate kernel)
+static const char* const kSolverTypeNames[] = {"SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta", "Adam"};
+static const char* const kSolverTypeEnum[] = {"SGD", "NESTEROV", "ADAGRAD", "RMSPROP", "ADADELTA", "ADAM"};
+
+template <typename Dtype>
+const char* Solver<Dtype>::type() const {
+  return kSolverTypeNames[kind_];
+}
+
+// solver_factory.hpp / upgrade_proto.cpp:1017-1060: `type` (default "SGD"),
+// or the deprecated `solver_type` enum (caffe.proto:233-242); then the
+// classes' constructor checks (sgd_solvers.hpp:77,97-101) and the solver-wide
+// scalars, `optional float` in caffe.proto (:217-223), so rounded to fp32
+template <typename Dtype>
+void Solver<Dtype>::InitSolverType() {
+  int by_type = -1, by_enum = -1;
+  if (param_.has("type")) {
+    const std::string t = param_.str("type");
+    for (int k = 0; k < 6; ++k)
+      if (t == kSolverTypeNames[k]) by_type = k;
+    CAFFE_CHECK(by_type >= 0, "Unknown solver type: " << t
+                                  << " (known types: SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam)");
+  }
+  if (param_.has("solver_type")) {
+    const std::string t = param_.str("solver_type");
+    for (int k = 0; k < 6; ++k)
+      if (t == kSolverTypeEnum[k] || t == std::to_string(k)) by_enum = k;
+    CAFFE_CHECK(by_enum >= 0, "Unknown solver_type: " << t
+                                  << " (known values: SGD, NESTEROV, ADAGRAD, RMSPROP, ADADELTA, ADAM)");
+  }
+  CAFFE_CHECK(by_type < 0 || by_enum < 0 || by_type == by_enum,
+              "solver type: \"" << param_.str("type") << "\" and the deprecated solver_type: "
+                                << param_.str("solver_type") << " disagree");
+  kind_ = by_type >= 0 ? by_type : (by_enum >= 0 ? by_enum : RRAM_SOLVER_SGD);
+  hyper_.momentum = static_cast<float>(param_.num("momentum", 0.0));
+  hyper_.delta = static_cast<float>(param_.num("delta", 1e-8));
+  hyper_.momentum2 = static_cast<float>(param_.num("momentum2", 0.999));
+  if (kind_ == RRAM_SOLVER_ADAGRAD) CAFFE_CHECK(hyper_.momentum == 0.0f, "Momentum cannot be used with AdaGrad.");
+  if (kind_ == RRAM_SOLVER_RMSPROP) {
+    CAFFE_CHECK(hyper_.momentum == 0.0f, "Momentum cannot be used with RMSProp.");
+    const float rms_decay = static_cast<float>(param_.num("rms_decay", 0.99));
+    CAFFE_CHECK(rms_decay >= 0.0f && rms_decay < 1.0f, "rms_decay should lie between 0 and 1 (rms_decay: " << rms_decay << ")");
+    hyper_.momentum2 = rms_decay;  // the decay rate of RMSProp's one history
+  }
+}
+
+// adam_solver.cpp:39-41: t = iter_ + 1, correction = std::sqrt(Dtype(1) -
+// pow(beta2, t)) / (Dtype(1.) - pow(beta1, t)).  The unqualified pow(float,
+// int) promotes to double, so the subtractions, the sqrt and the division run
+// in double too; the result is stored to fp32 and local_rate * correction
+// (adam_solver.cpp:72) is an fp32 product.
+template <typename Dtype>
+Dtype Solver<Dtype>::AdamCorrection() const {
+  const int t = iter_ + 1;
+  const double b1 = hyper_.momentum, b2 = hyper_.momentum2;
+  return (Dtype)(std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
+}
+
+template <typename Dtype>
+Dtype Solver<Dtype>::LocalRate(int id, Dtype rate) const {
+  const Dtype local = rate * net_->params_lr()[id];
+  return kind_ == RRAM_SOLVER_ADAM ? local * AdamCorrection() : local;
+}
+
+// sgd_solver.cpp:216-247 and the other classes' ComputeUpdateValue (GPU
+// branch: one update kernel per type)
 template <typename Dtype>
 void Solver<Dtype>::ComputeUpdateValue(int id, Dtype rate) {
   auto* p = net_->learnable_params()[id];
-  const Dtype local = rate * net_->params_lr()[id];
-  RRAM_CALL(rram_sgd_update(p->mutable_gpu_diff(), history_[id]->mutable_gpu_data(), p->count(),
-                            (Dtype)param_.num("momentum", 0.0), local, Caffe::stream()));
+  const Dtype local = LocalRate(id, rate);
+  Dtype* g = p->mutable_gpu_diff();
+  Dtype* h = history_[id]->mutable_gpu_data();
+  const int64_t n = p->count();
+  const size_t second = net_->learnable_params().size();  // update_history_offset
+  switch (kind_) {
+    case RRAM_SOLVER_SGD:
+      RRAM_CALL(rram_sgd_update(g, h, n, (Dtype)param_.num("momentum", 0.0), local, Caffe::stream()));
+      break;
+    case RRAM_SOLVER_NESTEROV:
+      RRAM_CALL(rram_nesterov_update(g, h, n, hyper_.momentum, local, Caffe::stream()));
+      break;
+    case RRAM_SOLVER_ADAGRAD:
+      RRAM_CALL(rram_adagrad_update(g, h, n, hyper_.delta, local, Caffe::stream()));
+      break;
+    case RRAM_SOLVER_RMSPROP:
+      RRAM_CALL(rram_rmsprop_update(g, h, n, hyper_.momentum2, hyper_.delta, local, Caffe::stream()));
+      break;
+    case RRAM_SOLVER_ADADELTA:
+      RRAM_CALL(rram_adadelta_update(g, h, history_[id + second]->mutable_gpu_data(), n, hyper_.momentum, hyper_.delta,
+                                     local, Caffe::stream()));
+      break;
+    case RRAM_SOLVER_ADAM:
+      RRAM_CALL(rram_adam_update(g, h, history_[id + second]->mutable_gpu_data(), n, hyper_.momentum, hyper_.momentum2,
+                                 hyper_.delta, local, Caffe::stream()));
+      break;
+    default:
+      throw Error("unknown solver kind");
+  }
 }
 
 // sgd_solver.cpp:101-116 (Normalize for iter_size > 1 folded into a scale)
@@ -387,7 +483,12 @@ void Solver<Dtype>::FusedTail() {
       }
     }
   std::vector<SyncedMemory*> flipped;
+  // SGD keeps its own entry and kernel; the other types go through
+  // rram_fused_opt_update_fail_batched, whose segment is the same plus h2
+  const bool sgd = kind_ == RRAM_SOLVER_SGD;
+  const bool two = kind_ == RRAM_SOLVER_ADADELTA || kind_ == RRAM_SOLVER_ADAM;
   std::vector<rram_update_seg> segs;
+  std::vector<rram_opt_seg> osegs;
   for (int i = 0; i < (int)ps.size(); ++i) {
     int f = -1;
     for (int k = 0; k < (int)fids.size(); ++k)
@@ -401,7 +502,7 @@ void Solver<Dtype>::FusedTail() {
     sg.values = faulty ? fi[f]->gpu_diff() : nullptr;
     sg.n = ps[i]->count();
     sg.decay = wd * net_->params_weight_decay()[i];
-    sg.local_rate = rate * net_->params_lr()[i];
+    sg.local_rate = LocalRate(i, rate);
     sg.apply_thr = (faulty && thr) ? 1 : 0;
     sg.thr = (faulty && thr) ? thr->threshold_for(f) : 0.0f;
     sg.broken_count = (faulty && counts) ? counts + f : nullptr;
@@ -415,11 +516,37 @@ void Solver<Dtype>::FusedTail() {
         flipped.push_back(fl.m);
         break;
       }
-    segs.push_back(sg);
+    if (sgd) {
+      segs.push_back(sg);
+      continue;
+    }
+    rram_opt_seg og{};
+    og.w = sg.w;
+    og.g = sg.g;
+    og.h = sg.h;
+    og.endurance = sg.endurance;
+    og.values = sg.values;
+    og.n = sg.n;
+    og.decay = sg.decay;
+    og.local_rate = sg.local_rate;
+    og.thr = sg.thr;
+    og.apply_thr = sg.apply_thr;
+    og.broken_count = sg.broken_count;
+    og.w_flip = sg.w_flip;
+    og.flip_groups = sg.flip_groups;
+    og.flip_cin = sg.flip_cin;
+    og.flip_cout = sg.flip_cout;
+    og.flip_taps = sg.flip_taps;
+    og.h2 = two ? history_[i + ps.size()]->mutable_gpu_data() : nullptr;
+    osegs.push_back(og);
   }
   for (size_t b = 0; b < segs.size(); b += RRAM_MAX_SEGS)
     RRAM_CALL(rram_fused_update_fail_batched(segs.data() + b, (int)std::min<size_t>(RRAM_MAX_SEGS, segs.size() - b), mom,
                                              gm ? gm->decrement : 100.0f, gm ? gm->epsilon : 1e-20f, Caffe::stream()));
+  for (size_t b = 0; b < osegs.size(); b += RRAM_MAX_SEGS)
+    RRAM_CALL(rram_fused_opt_update_fail_batched(osegs.data() + b, (int)std::min<size_t>(RRAM_MAX_SEGS, osegs.size() - b),
+                                                 kind_, &hyper_, gm ? gm->decrement : 100.0f,
+                                                 gm ? gm->epsilon : 1e-20f, Caffe::stream()));
   for (SyncedMemory* m : flipped) m->set_wflip_valid(epoch);
 }
 
@@ -534,7 +661,11 @@ void Solver<Dtype>::Step(int iters) {
     const bool disp = display && iter_ % display == 0;
     // (a learning rate that moves every iteration, e.g. lr_policy "inv",
     // keeps the eager path: a graph is only worth its capture when replayed)
-    const Dtype rate_now = graph_ ? GetLearningRate() : Dtype(0);
+    // (Adam's bias correction moves its rate every iteration in the same way:
+    // the corrected rate is the rate here, so Adam stays eager until the
+    // correction has converged in fp32)
+    const Dtype rate_now =
+        graph_ ? (kind_ == RRAM_SOLVER_ADAM ? GetLearningRate() * AdamCorrection() : GetLearningRate()) : Dtype(0);
     const bool rate_stable = rate_now == graph_prev_rate_;
     graph_prev_rate_ = rate_now;
     if (graph_ && rate_stable && can_fuse && !test_now && !disp && average_loss <= 1 && !net_->on_backward_layer &&

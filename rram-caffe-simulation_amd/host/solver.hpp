@@ -219,8 +219,13 @@ class Solver {
   std::shared_ptr<FailureMaker<Dtype>> failure_maker() { return fmaker_; }
   const std::vector<std::shared_ptr<FailureStrategy<Dtype>>>& strategies() const { return strategys_; }
   Dtype smoothed_loss() const { return smoothed_loss_; }
-  // SGDSolver::history() (sgd_solver.hpp:29): momentum history, one blob per learnable param
+  // SGDSolver::history() (sgd_solver.hpp:29): one history blob per learnable
+  // param; AdaDelta and Adam append a second set (adadelta_solver.cpp:8-16,
+  // adam_solver.cpp:8-17), history()[i + nparams] pairing with param i
   const std::vector<std::unique_ptr<Blob<Dtype>>>& history() const { return history_; }
+  // Solver::type() (sgd_solvers.hpp): "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta", "Adam"
+  const char* type() const;
+  int kind() const { return kind_; }  // RRAM_SOLVER_*
   // Solver::Callback::on_gradients_ready (solver.hpp:80-91): the data-parallel
   // hook (RCCL all-reduce of the flat gradient buffer).
   std::function<void()> on_gradients_ready;
@@ -254,6 +259,7 @@ class Solver {
   template <typename F>
   void capture_launch(int k, F&& body);
   void InitFailurePattern(const Msg& failure_param);
+  void InitSolverType();
   void ComputeUpdate();
   void ApplyStrategy();
   void ApplyUpdate();
@@ -264,6 +270,10 @@ class Solver {
   void ClipGradients();
   void Regularize(int param_id);
   void ComputeUpdateValue(int param_id, Dtype rate);
+  // the rate the type's update kernel takes for param_id: rate * lr_mult, for
+  // Adam times the bias correction of this iteration
+  Dtype LocalRate(int param_id, Dtype rate) const;
+  Dtype AdamCorrection() const;
   void emit(const std::string& s) {
     if (log) log(s);
   }
@@ -286,6 +296,8 @@ class Solver {
   Dtype smoothed_loss_ = 0;
   std::vector<Dtype> losses_;
   bool fused_update_ = false;
+  int kind_ = RRAM_SOLVER_SGD;
+  rram_solver_hyper hyper_{};  // momentum / beta1, momentum2 / rms_decay, delta (fp32, caffe.proto's `optional float`)
   bool flip_cache_ = true;  // option conv_flip_cache: FusedTail writes the flipped kernels (rram_update_seg.w_flip)
 };
 

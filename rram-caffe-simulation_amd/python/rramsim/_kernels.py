@@ -59,6 +59,22 @@ class UpdateSeg(C.Structure):
                 ("flip_taps", C.c_int)]
 
 
+class OptSeg(C.Structure):
+    """rram_opt_seg: UpdateSeg plus the second history h2 (NULL for the one-history solver types)."""
+    _fields_ = UpdateSeg._fields_ + [("h2", C.c_void_p)]
+
+
+class SolverHyper(C.Structure):
+    """rram_solver_hyper: momentum / beta1, momentum2 / rms_decay, delta."""
+    _fields_ = [("momentum", C.c_float), ("momentum2", C.c_float), ("delta", C.c_float)]
+
+
+(RRAM_SOLVER_SGD, RRAM_SOLVER_NESTEROV, RRAM_SOLVER_ADAGRAD, RRAM_SOLVER_RMSPROP, RRAM_SOLVER_ADADELTA,
+ RRAM_SOLVER_ADAM) = range(6)
+SOLVER_KINDS = {"SGD": RRAM_SOLVER_SGD, "Nesterov": RRAM_SOLVER_NESTEROV, "AdaGrad": RRAM_SOLVER_ADAGRAD,
+                "RMSProp": RRAM_SOLVER_RMSPROP, "AdaDelta": RRAM_SOLVER_ADADELTA, "Adam": RRAM_SOLVER_ADAM}
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in (
         "num", "channels", "height", "width", "num_output", "kernel_h", "kernel_w", "pad_h",
@@ -95,6 +111,13 @@ SIGNATURES = {
     "rram_sgd_update": (I, [P, P, I64, F, F, P]),
     "rram_fused_update_fail": (I, [P, P, P, P, P, I64, F, F, F, I, F, F, F, P, P]),
     "rram_fused_update_fail_batched": (I, [P, I, F, F, F, P]),
+    "rram_nesterov_update": (I, [P, P, I64, F, F, P]),
+    "rram_adagrad_update": (I, [P, P, I64, F, F, P]),
+    "rram_rmsprop_update": (I, [P, P, I64, F, F, F, P]),
+    "rram_adadelta_update": (I, [P, P, P, I64, F, F, F, P]),
+    "rram_adam_update": (I, [P, P, P, I64, F, F, F, F, P]),
+    "rram_fused_opt_update_fail": (I, [P, P, P, P, P, P, I64, I, P, F, F, I, F, F, F, P, P]),
+    "rram_fused_opt_update_fail_batched": (I, [P, I, I, P, F, F, P]),
     "rram_axpy": (I, [I64, F, P, P, P]),
     "rram_axpby": (I, [I64, F, P, F, P, P]),
     "rram_scal": (I, [I64, F, P, P]),

@@ -67,6 +67,7 @@ SIGNATURES = {
     "rram_solver_iter": (I, [P, PI]),
     "rram_solver_smoothed_loss": (I, [P, PF]),
     "rram_solver_learning_rate": (I, [P, PF]),
+    "rram_solver_type": (I, [P, C.c_char_p, I]),
     "rram_solver_net": (I, [P, PP]),
     "rram_solver_num_test_nets": (I, [P, PI]),
     "rram_solver_test_net": (I, [P, I, PP]),
@@ -465,7 +466,9 @@ class Net:
 
 
 class Solver:
-    """caffe::SGDSolver with the fork's fault hooks."""
+    """caffe::SGDSolver and its five subclasses (Nesterov, AdaGrad, RMSProp,
+    AdaDelta, Adam; prototxt `type` or the deprecated `solver_type`) with the
+    fork's fault hooks."""
 
     def __init__(self, solver_prototxt: str, net_prototxt: Optional[str] = None,
                  options: Optional[Dict] = None, log=None):
@@ -514,6 +517,13 @@ class Solver:
         v = C.c_int()
         check(self._lib.rram_solver_iter(self.h, C.byref(v)), "iter")
         return v.value
+
+    @property
+    def type(self) -> str:
+        """Solver::type(): "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta" or "Adam"."""
+        buf = C.create_string_buffer(32)
+        check(self._lib.rram_solver_type(self.h, buf, 32), "solver_type")
+        return buf.value.decode()
 
     def learning_rate(self) -> float:
         v = C.c_float()
@@ -606,7 +616,10 @@ class Solver:
         return [buf[i] for i in range(n.value)]
 
     def history(self):
-        """SGDSolver::history(): momentum blob per learnable param (device views)."""
+        """SGDSolver::history() as device views: one history blob per learnable
+        param, in param order.  AdaDelta and Adam keep two per param, 2 * nparams
+        in all: history()[i + nparams] is the second history of param i
+        (AdaDelta's squared-update average, Adam's v)."""
         n = C.c_int()
         check(self._lib.rram_solver_num_history(self.h, C.byref(n)), "num_history")
         out = []

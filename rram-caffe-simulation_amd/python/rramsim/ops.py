@@ -144,6 +144,58 @@ def fused_update_fail_batched(segs, momentum, decrement=100.0, eps=1e-20):
             "fused_update_fail_batched")
 
 
+def nesterov_update(g, h, momentum, local_rate):
+    K.check(_lib().rram_nesterov_update(_p(g), _p(h), g.numel(), momentum, local_rate, _stream()), "nesterov_update")
+
+
+def adagrad_update(g, h, delta, local_rate):
+    K.check(_lib().rram_adagrad_update(_p(g), _p(h), g.numel(), delta, local_rate, _stream()), "adagrad_update")
+
+
+def rmsprop_update(g, h, rms_decay, delta, local_rate):
+    K.check(_lib().rram_rmsprop_update(_p(g), _p(h), g.numel(), rms_decay, delta, local_rate, _stream()),
+            "rmsprop_update")
+
+
+def adadelta_update(g, h, h2, momentum, delta, local_rate):
+    K.check(_lib().rram_adadelta_update(_p(g), _p(h), _p(h2), g.numel(), momentum, delta, local_rate, _stream()),
+            "adadelta_update")
+
+
+def adam_update(g, m, v, beta1, beta2, eps_hat, corrected_local_rate):
+    K.check(_lib().rram_adam_update(_p(g), _p(m), _p(v), g.numel(), beta1, beta2, eps_hat, corrected_local_rate,
+                                    _stream()), "adam_update")
+
+
+def solver_hyper(momentum=0.0, momentum2=0.999, delta=1e-8):
+    """rram_solver_hyper: momentum / beta1, momentum2 (beta2; rms_decay for RMSProp), delta / eps_hat."""
+    return K.SolverHyper(momentum, momentum2, delta)
+
+
+def fused_opt_update_fail(kind, hyper, w, g, h, h2, e, v, decay, lr, apply_thr, thr, decrement=100.0, eps=1e-20,
+                          counter=None):
+    """The fused tail of one blob for solver type `kind` (K.RRAM_SOLVER_*); h2 None for the one-history types."""
+    K.check(_lib().rram_fused_opt_update_fail(_p(w), _p(g), _p(h), _p(h2), _p(e), _p(v), w.numel(), int(kind),
+                                              C.byref(hyper), decay, lr, int(apply_thr), thr, decrement, eps,
+                                              _p(counter), _stream()), "fused_opt_update_fail")
+
+
+def fused_opt_update_fail_batched(kind, hyper, segs, decrement=100.0, eps=1e-20):
+    """segs: list of (w, g, h, h2, e, v, decay, lr, apply_thr, thr, counter[, (w_flip, groups, cin, cout, taps)]);
+    one launch."""
+    arr = (K.OptSeg * len(segs))()
+    for i, sg in enumerate(segs):
+        w, g, h, h2, e, v, decay, lr, apply_thr, thr, counter = sg[:11]
+        for t, nm in ((w, "w"), (g, "g"), (h, "h"), (h2, "h2"), (e, "endurance"), (v, "values")):
+            _f32(t, nm)
+        flip = sg[11] if len(sg) > 11 and sg[11] is not None else (None, 0, 0, 0, 0)
+        _f32(flip[0], "w_flip")
+        arr[i] = K.OptSeg(_p(w), _p(g), _p(h), _p(e), _p(v), w.numel(), decay, lr, thr, int(apply_thr), _p(counter),
+                          _p(flip[0]), *flip[1:], _p(h2))
+    K.check(_lib().rram_fused_opt_update_fail_batched(arr, len(segs), int(kind), C.byref(hyper), decrement, eps,
+                                                      _stream()), "fused_opt_update_fail_batched")
+
+
 def gemm(trans_a, trans_b, M, N, K_, alpha, A, B, beta, Cm):
     K.check(_lib().rram_gemm_f32(int(trans_a), int(trans_b), M, N, K_, alpha, _p(A), _p(B), beta,
                                  _p(Cm), _stream()), "gemm")
