@@ -242,7 +242,10 @@ int rram_fused_update_fail(float* w, float* g, float* h, float* endurance,
  * was one launch per blob).  Per segment: the arguments of
  * rram_fused_update_fail; momentum, decrement and eps are solver-wide.
  * Element-wise identical arithmetic, so bit-identical to nsegs calls of
- * rram_fused_update_fail; broken_count may repeat across segments. */
+ * rram_fused_update_fail; broken_count may repeat across segments.
+ * rram_sgd_update and both fused SGD entries are the RRAM_SOLVER_SGD case of
+ * the one update and the one tail kernel of all solver types (below);
+ * rram_update_seg is rram_opt_seg without its last field h2. */
 typedef struct rram_update_seg {
   float* w;
   float* g;
@@ -295,7 +298,8 @@ int rram_adam_update(float* g, float* m, float* v, int64_t n, float beta1, float
  * reference's order (sgd_solver.cpp:101-116, solver.cpp:299-305):
  *   g += decay * w; g = <the type's update>(g, h, h2); if (|g| <= thr) g = 0;
  *   w -= g; FailKernel(e, v, w, g); the optional w_flip write.
- * RRAM_SOLVER_SGD computes what rram_fused_update_fail_batched computes. */
+ * One kernel, the type its template parameter: RRAM_SOLVER_SGD is what
+ * rram_fused_update_fail_batched launches. */
 enum {
   RRAM_SOLVER_SGD = 0,
   RRAM_SOLVER_NESTEROV = 1,

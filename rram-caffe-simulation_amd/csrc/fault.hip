@@ -5,7 +5,9 @@
 // 256-thread blocks, grid-stride, wave-level ballot reductions for counters.
 #include <atomic>
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "rram_common.hpp"
 
@@ -506,119 +508,9 @@ __global__ void __launch_bounds__(256)
   wave_count_add_n(cnt, cleared);
 }
 
-__global__ void __launch_bounds__(256)
-    k_sgd_update(float* __restrict__ g, float* __restrict__ h, int64_t n, float mom, float lr) {
-  // Caffe's CPU path forms momentum*h and local_rate*g as separate products
-  // (caffe_cpu_axpby = scal + axpy, sgd_solver.cpp:222-228); the oracle does the
-  // same, so no FMA contraction here or in the fused tail / axpby below.
-#pragma clang fp contract(off)
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = mom * h[i] + lr * g[i];
-    g[i] = v;
-    h[i] = v;
-  }
-}
-
-__global__ void __launch_bounds__(256)
-    k_fused_update_fail(float* __restrict__ w, float* __restrict__ g, float* __restrict__ h,
-                        float* __restrict__ e, const float* __restrict__ v, int64_t n, float decay,
-                        float mom, float lr, int apply_thr, float thr, float dec, float eps,
-                        unsigned long long* counter) {
-#pragma clang fp contract(off)
-  unsigned cnt = 0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float wi = w[i];
-    float gi = g[i];
-    if (decay != 0.0f) gi = decay * wi + gi;            // caffe_gpu_axpy(decay, w, g)
-    gi = mom * h[i] + lr * gi;                          // SGDUpdate
-    h[i] = gi;
-    if (apply_thr && fabsf(gi) <= thr) gi = 0.0f;       // threshold strategy
-    g[i] = gi;
-    wi = wi - gi;                                       // Blob::Update (axpy -1)
-    if (e != nullptr) {
-      float ee = e[i];
-      bool wr;
-      float wv;
-      cnt += fail_one(gi, wv, ee, v[i], dec, eps, wr);
-      e[i] = ee;
-      if (wr) wi = wv;
-    }
-    w[i] = wi;
-  }
-  wave_count_add_n(cnt, counter);
-}
-
-// k_fused_update_fail over all of a net's learnable blobs: block-chunks of
-// kUpdChunk elements dealt across the segments (as k_fail_apply_batched), the
-// per-element arithmetic k_fused_update_fail's
-struct UpdateSegs {
-  rram_update_seg s[RRAM_MAX_SEGS];
-  int64_t chunk_start[RRAM_MAX_SEGS + 1];
-  int nsegs;
-};
-constexpr int kUpdChunk = 256 * 8;
-
-__global__ void __launch_bounds__(256)
-    k_fused_update_fail_batched(UpdateSegs segs, float mom, float dec, float eps) {
-#pragma clang fp contract(off)
-  const int64_t total = segs.chunk_start[segs.nsegs];
-  int cur = -1;  // block-uniform: flush the count once per segment visited
-  unsigned cnt = 0;
-  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
-    int s = 0;
-    while (c >= segs.chunk_start[s + 1]) ++s;
-    if (s != cur) {
-      if (cur >= 0) block_count_flush(cnt, segs.s[cur].broken_count);
-      cnt = 0;
-      cur = s;
-    }
-    const rram_update_seg& sg = segs.s[s];
-    const int64_t begin = (c - segs.chunk_start[s]) * kUpdChunk;
-    const int64_t end = min(begin + (int64_t)kUpdChunk, sg.n);
-    float* __restrict__ w = sg.w;
-    float* __restrict__ g = sg.g;
-    float* __restrict__ h = sg.h;
-    float* __restrict__ e = sg.endurance;
-    const float* __restrict__ v = sg.values;
-    for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-      float wi = w[i];
-      float gi = g[i];
-      if (sg.decay != 0.0f) gi = sg.decay * wi + gi;
-      gi = mom * h[i] + sg.local_rate * gi;
-      h[i] = gi;
-      if (sg.apply_thr && fabsf(gi) <= sg.thr) gi = 0.0f;
-      g[i] = gi;
-      wi = wi - gi;
-      if (e != nullptr) {
-        float ee = e[i];
-        bool wr;
-        float wv;
-        cnt += fail_one(gi, wv, ee, v[i], dec, eps, wr);
-        e[i] = ee;
-        if (wr) wi = wv;
-      }
-      w[i] = wi;
-      if (sg.w_flip != nullptr) {  // (the host checked G cin cout taps == n < 2^31)
-        const int T = sg.flip_taps, ci = sg.flip_cin, co = sg.flip_cout;
-        int t = static_cast<int>(i);
-        const int tap = t % T;
-        t /= T;
-        const int c = t % ci;
-        t /= ci;
-        const int o = t % co;
-        const int gr = t / co;
-        sg.w_flip[((gr * ci + c) * co + o) * T + (T - 1 - tap)] = wi;
-      }
-    }
-  }
-  if (cur >= 0) block_count_flush(cnt, segs.s[cur].broken_count);
-}
-
 // ---------------------------------------------------------------------------
-// The five non-SGD solver types (src/caffe/solvers/*_solver.cu): the .cu
-// files' expressions, literally, in fp32, left to right, every product and sum
+// The six solver types (src/caffe/solvers/*_solver.cu): the .cu files'
+// expressions, literally, in fp32, left to right, every product and sum
 // rounded on its own.  a = momentum / beta1 (rms_decay for RMSProp),
 // b = momentum2 / beta2, h2 only for AdaDelta and Adam.  Returns the update
 // value (the new g[i]); h and h2 are the element's histories, in and out.
@@ -627,7 +519,10 @@ template <int KIND>
 __device__ __forceinline__ float opt_update(float gi, float& h, float& h2, float a, float b, float delta,
                                             float lr) {
 #pragma clang fp contract(off)
-  if (KIND == RRAM_SOLVER_SGD) {  // sgd_solver.cu:6-12 (k_sgd_update)
+  if (KIND == RRAM_SOLVER_SGD) {  // sgd_solver.cu:6-12
+    // Caffe's CPU path forms momentum*h and local_rate*g as separate products
+    // (caffe_cpu_axpby = scal + axpy, sgd_solver.cpp:222-228); the oracle does the
+    // same, so no FMA contraction here, in the fused tail or in axpby below.
     const float v = a * h + lr * gi;
     h = v;
     return v;
@@ -676,20 +571,22 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// k_fused_update_fail_batched for any solver type: the same dealing of
-// kUpdChunk block-chunks across the segments and the same per-element order
-// (decay, the type's update, threshold, w -= g, Fail, flipped kernel), the
-// type a template parameter.  A pure stream: 9 floats per faultable element
-// for the one-history types (w g h e in and out, v in), 11 with h2.
+// The fused training tail over all of a net's learnable blobs, for every
+// solver type (SGD is KIND == RRAM_SOLVER_SGD): block-chunks of kUpdChunk
+// elements dealt across the segments (as k_fail_apply_batched), per element
+// decay, the type's update, threshold, w -= g, Fail, flipped kernel.  A pure
+// stream: 9 floats per faultable element for the one-history types (w g h e
+// in and out, v in), 11 with h2.
 struct OptSegs {
   rram_opt_seg s[RRAM_MAX_SEGS];
   int64_t chunk_start[RRAM_MAX_SEGS + 1];
   int nsegs;
 };
+constexpr int kUpdChunk = 256 * 8;
 
 template <int KIND>
 __global__ void __launch_bounds__(256)
-    k_fused_opt_update_fail_batched(OptSegs segs, float a, float b, float delta, float dec, float eps) {
+    k_fused_update_fail_batched(OptSegs segs, float a, float b, float delta, float dec, float eps) {
 #pragma clang fp contract(off)
   const int64_t total = segs.chunk_start[segs.nsegs];
   int cur = -1;  // block-uniform: flush the count once per segment visited
@@ -1134,6 +1031,55 @@ static int launch_opt_update(const char* what, float* g, float* h, float* h2, in
   return launch_status(what);
 }
 
+// The one fused tail behind the four rram_fused_*update_fail* entries: checks
+// the segments, deals their kUpdChunk chunks and launches the kernel of
+// `kind`.  `what` names the entry the caller called.  a, b, delta as in
+// opt_update.
+static int launch_fused_tail(const char* what, const rram_opt_seg* segs, int nsegs, int kind, float a, float b,
+                             float delta, float dec, float eps, rram_stream_t s) {
+  using namespace rram;
+  RRAM_REQUIRE(nsegs >= 0 && nsegs <= RRAM_MAX_SEGS, "%s: nsegs out of range", what);
+  RRAM_REQUIRE(kind >= RRAM_SOLVER_SGD && kind <= RRAM_SOLVER_ADAM, "%s: solver kind %d", what, kind);
+  if (nsegs == 0) return RRAM_OK;
+  RRAM_REQUIRE(segs, "%s: segs is NULL", what);
+  OptSegs us{};
+  us.nsegs = nsegs;
+  for (int i = 0; i < nsegs; ++i) {
+    const rram_opt_seg& sg = segs[i];
+    RRAM_REQUIRE(sg.n >= 0, "%s: segment %d n < 0", what, i);
+    if (sg.n > 0) RRAM_REQUIRE(sg.w && sg.g && sg.h, "%s: segment %d NULL pointer", what, i);
+    if (sg.n > 0 && opt_two_histories(kind))
+      RRAM_REQUIRE(sg.h2, "%s: segment %d h2 is NULL (AdaDelta and Adam keep two histories)", what, i);
+    RRAM_REQUIRE((sg.endurance == nullptr) == (sg.values == nullptr), "%s: segment %d endurance/values mismatch", what,
+                 i);
+    if (sg.w_flip != nullptr)
+      RRAM_REQUIRE(sg.flip_groups > 0 && sg.flip_cin > 0 && sg.flip_cout > 0 && sg.flip_taps > 0 &&
+                       (int64_t)sg.flip_groups * sg.flip_cin * sg.flip_cout * sg.flip_taps == sg.n && sg.n < (1ll << 31),
+                   "%s: segment %d flip geometry %d x %d x %d x %d != n %lld", what, i, sg.flip_groups, sg.flip_cin,
+                   sg.flip_cout, sg.flip_taps, (long long)sg.n);
+    us.s[i] = sg;
+    us.chunk_start[i + 1] = us.chunk_start[i] + (sg.n + kUpdChunk - 1) / kUpdChunk;
+  }
+  const int64_t total = us.chunk_start[nsegs];
+  if (total == 0) return RRAM_OK;
+  const int grid = static_cast<int>(total < 2048 ? total : 2048);
+#define RRAM_TAIL_LAUNCH(K)                                                                                           \
+  case K:                                                                                                             \
+    hipLaunchKernelGGL(k_fused_update_fail_batched<K>, dim3(grid), dim3(kThreads), 0, as_stream(s), us, a, b, delta, \
+                       dec, eps);                                                                                     \
+    break;
+  switch (kind) {
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_SGD)
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_NESTEROV)
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_ADAGRAD)
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_RMSPROP)
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_ADADELTA)
+    RRAM_TAIL_LAUNCH(RRAM_SOLVER_ADAM)
+  }
+#undef RRAM_TAIL_LAUNCH
+  return launch_status(what);
+}
+
 extern "C" {
 
 int rram_inject_rng(const float* w_clean, float* w_out, int64_t n, const rram_inject_cfg* cfg,
@@ -1177,53 +1123,46 @@ int rram_threshold_strategy(float* dw, int64_t n, float thr, unsigned long long*
 }
 
 int rram_sgd_update(float* g, float* h, int64_t n, float mom, float lr, rram_stream_t s) {
-  RRAM_REQUIRE(n >= 0, "sgd_update: n < 0");
-  if (n == 0) return RRAM_OK;
-  RRAM_REQUIRE(g && h, "sgd_update: NULL pointer");
-  hipLaunchKernelGGL(k_sgd_update, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), g, h,
-                     n, mom, lr);
-  return launch_status("sgd_update");
+  return launch_opt_update<RRAM_SOLVER_SGD>("sgd_update", g, h, nullptr, n, mom, 0.0f, 0.0f, lr, s);
 }
 
 int rram_fused_update_fail(float* w, float* g, float* h, float* e, const float* v, int64_t n,
                            float decay, float mom, float lr, int apply_thr, float thr, float dec,
                            float eps, unsigned long long* counter, rram_stream_t s) {
-  RRAM_REQUIRE(n >= 0, "fused_update_fail: n < 0");
-  if (n == 0) return RRAM_OK;
-  RRAM_REQUIRE(w && g && h, "fused_update_fail: NULL pointer");
-  RRAM_REQUIRE((e == nullptr) == (v == nullptr), "fused_update_fail: endurance/values mismatch");
-  hipLaunchKernelGGL(k_fused_update_fail, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s),
-                     w, g, h, e, v, n, decay, mom, lr, apply_thr, thr, dec, eps, counter);
-  return launch_status("fused_update_fail");
+  rram_update_seg sg{};
+  sg.w = w;
+  sg.g = g;
+  sg.h = h;
+  sg.endurance = e;
+  sg.values = v;
+  sg.n = n;
+  sg.decay = decay;
+  sg.local_rate = lr;
+  sg.thr = thr;
+  sg.apply_thr = apply_thr;
+  sg.broken_count = counter;
+  return rram_fused_update_fail_batched(&sg, 1, mom, dec, eps, s);
 }
+
+// rram_update_seg is the prefix of rram_opt_seg, which adds h2 alone
+#define RRAM_SAME_OFFSET(f) static_assert(offsetof(rram_update_seg, f) == offsetof(rram_opt_seg, f), #f)
+RRAM_SAME_OFFSET(w); RRAM_SAME_OFFSET(g); RRAM_SAME_OFFSET(h); RRAM_SAME_OFFSET(endurance);
+RRAM_SAME_OFFSET(values); RRAM_SAME_OFFSET(n); RRAM_SAME_OFFSET(decay); RRAM_SAME_OFFSET(local_rate);
+RRAM_SAME_OFFSET(thr); RRAM_SAME_OFFSET(apply_thr); RRAM_SAME_OFFSET(broken_count); RRAM_SAME_OFFSET(w_flip);
+RRAM_SAME_OFFSET(flip_groups); RRAM_SAME_OFFSET(flip_cin); RRAM_SAME_OFFSET(flip_cout); RRAM_SAME_OFFSET(flip_taps);
+#undef RRAM_SAME_OFFSET
+static_assert(offsetof(rram_opt_seg, h2) == sizeof(rram_update_seg) &&
+                  sizeof(rram_opt_seg) == sizeof(rram_update_seg) + sizeof(float*),
+              "rram_opt_seg = rram_update_seg + h2");
 
 int rram_fused_update_fail_batched(const rram_update_seg* segs, int nsegs, float mom, float dec, float eps,
                                    rram_stream_t s) {
-  using namespace rram;
-  RRAM_REQUIRE(nsegs >= 0 && nsegs <= RRAM_MAX_SEGS, "fused_update_fail_batched: nsegs out of range");
-  if (nsegs == 0) return RRAM_OK;
-  RRAM_REQUIRE(segs, "fused_update_fail_batched: segs is NULL");
-  UpdateSegs us{};
-  us.nsegs = nsegs;
-  for (int i = 0; i < nsegs; ++i) {
-    const rram_update_seg& sg = segs[i];
-    RRAM_REQUIRE(sg.n >= 0, "fused_update_fail_batched: segment %d n < 0", i);
-    if (sg.n > 0) RRAM_REQUIRE(sg.w && sg.g && sg.h, "fused_update_fail_batched: segment %d NULL pointer", i);
-    RRAM_REQUIRE((sg.endurance == nullptr) == (sg.values == nullptr),
-                 "fused_update_fail_batched: segment %d endurance/values mismatch", i);
-    if (sg.w_flip != nullptr)
-      RRAM_REQUIRE(sg.flip_groups > 0 && sg.flip_cin > 0 && sg.flip_cout > 0 && sg.flip_taps > 0 &&
-                       (int64_t)sg.flip_groups * sg.flip_cin * sg.flip_cout * sg.flip_taps == sg.n && sg.n < (1ll << 31),
-                   "fused_update_fail_batched: segment %d flip geometry %d x %d x %d x %d != n %lld", i, sg.flip_groups,
-                   sg.flip_cin, sg.flip_cout, sg.flip_taps, (long long)sg.n);
-    us.s[i] = sg;
-    us.chunk_start[i + 1] = us.chunk_start[i] + (sg.n + kUpdChunk - 1) / kUpdChunk;
-  }
-  const int64_t total = us.chunk_start[nsegs];
-  if (total == 0) return RRAM_OK;
-  const int grid = static_cast<int>(total < 2048 ? total : 2048);
-  hipLaunchKernelGGL(k_fused_update_fail_batched, dim3(grid), dim3(kThreads), 0, as_stream(s), us, mom, dec, eps);
-  return launch_status("fused_update_fail_batched");
+  // one prefix copy per segment, h2 left NULL; a bad nsegs or NULL segs is launch_fused_tail's to answer
+  rram_opt_seg wide[RRAM_MAX_SEGS] = {};
+  for (int i = 0; segs != nullptr && nsegs <= RRAM_MAX_SEGS && i < nsegs; ++i)
+    memcpy(&wide[i], &segs[i], sizeof(rram_update_seg));
+  return launch_fused_tail("fused_update_fail_batched", segs ? wide : nullptr, nsegs, RRAM_SOLVER_SGD, mom, 0.0f, 0.0f,
+                           dec, eps, s);
 }
 
 int rram_nesterov_update(float* g, float* h, int64_t n, float momentum, float local_rate, rram_stream_t s) {
@@ -1250,53 +1189,11 @@ int rram_adam_update(float* g, float* m, float* v, int64_t n, float beta1, float
 
 int rram_fused_opt_update_fail_batched(const rram_opt_seg* segs, int nsegs, int kind, const rram_solver_hyper* hyper,
                                        float dec, float eps, rram_stream_t s) {
-  using namespace rram;
-  RRAM_REQUIRE(nsegs >= 0 && nsegs <= RRAM_MAX_SEGS, "fused_opt_update_fail_batched: nsegs out of range");
-  RRAM_REQUIRE(kind >= RRAM_SOLVER_SGD && kind <= RRAM_SOLVER_ADAM, "fused_opt_update_fail_batched: solver kind %d",
-               kind);
   RRAM_REQUIRE(hyper, "fused_opt_update_fail_batched: hyper is NULL");
-  if (nsegs == 0) return RRAM_OK;
-  RRAM_REQUIRE(segs, "fused_opt_update_fail_batched: segs is NULL");
-  OptSegs us{};
-  us.nsegs = nsegs;
-  for (int i = 0; i < nsegs; ++i) {
-    const rram_opt_seg& sg = segs[i];
-    RRAM_REQUIRE(sg.n >= 0, "fused_opt_update_fail_batched: segment %d n < 0", i);
-    if (sg.n > 0) RRAM_REQUIRE(sg.w && sg.g && sg.h, "fused_opt_update_fail_batched: segment %d NULL pointer", i);
-    if (sg.n > 0 && opt_two_histories(kind))
-      RRAM_REQUIRE(sg.h2, "fused_opt_update_fail_batched: segment %d h2 is NULL (AdaDelta and Adam keep two histories)",
-                   i);
-    RRAM_REQUIRE((sg.endurance == nullptr) == (sg.values == nullptr),
-                 "fused_opt_update_fail_batched: segment %d endurance/values mismatch", i);
-    if (sg.w_flip != nullptr)
-      RRAM_REQUIRE(sg.flip_groups > 0 && sg.flip_cin > 0 && sg.flip_cout > 0 && sg.flip_taps > 0 &&
-                       (int64_t)sg.flip_groups * sg.flip_cin * sg.flip_cout * sg.flip_taps == sg.n && sg.n < (1ll << 31),
-                   "fused_opt_update_fail_batched: segment %d flip geometry %d x %d x %d x %d != n %lld", i,
-                   sg.flip_groups, sg.flip_cin, sg.flip_cout, sg.flip_taps, (long long)sg.n);
-    us.s[i] = sg;
-    us.chunk_start[i + 1] = us.chunk_start[i] + (sg.n + kUpdChunk - 1) / kUpdChunk;
-  }
-  const int64_t total = us.chunk_start[nsegs];
-  if (total == 0) return RRAM_OK;
-  const int grid = static_cast<int>(total < 2048 ? total : 2048);
   // a: momentum / beta1, the decay rate of RMSProp's one history
   const float a = kind == RRAM_SOLVER_RMSPROP ? hyper->momentum2 : hyper->momentum;
-  const float b = hyper->momentum2, delta = hyper->delta;
-#define RRAM_OPT_LAUNCH(K)                                                                                          \
-  case K:                                                                                                           \
-    hipLaunchKernelGGL(k_fused_opt_update_fail_batched<K>, dim3(grid), dim3(kThreads), 0, as_stream(s), us, a, b, \
-                       delta, dec, eps);                                                                            \
-    break;
-  switch (kind) {
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_SGD)
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_NESTEROV)
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADAGRAD)
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_RMSPROP)
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADADELTA)
-    RRAM_OPT_LAUNCH(RRAM_SOLVER_ADAM)
-  }
-#undef RRAM_OPT_LAUNCH
-  return launch_status("fused_opt_update_fail_batched");
+  return launch_fused_tail("fused_opt_update_fail_batched", segs, nsegs, kind, a, hyper->momentum2, hyper->delta, dec,
+                           eps, s);
 }
 
 int rram_fused_opt_update_fail(float* w, float* g, float* h, float* h2, float* e, const float* v, int64_t n, int kind,

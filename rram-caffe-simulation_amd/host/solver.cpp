@@ -395,7 +395,7 @@ void Solver<Dtype>::ComputeUpdateValue(int id, Dtype rate) {
   const size_t second = net_->learnable_params().size();  // update_history_offset
   switch (kind_) {
     case RRAM_SOLVER_SGD:
-      RRAM_CALL(rram_sgd_update(g, h, n, (Dtype)param_.num("momentum", 0.0), local, Caffe::stream()));
+      RRAM_CALL(rram_sgd_update(g, h, n, hyper_.momentum, local, Caffe::stream()));
       break;
     case RRAM_SOLVER_NESTEROV:
       RRAM_CALL(rram_nesterov_update(g, h, n, hyper_.momentum, local, Caffe::stream()));
@@ -452,7 +452,6 @@ void Solver<Dtype>::FusedTail() {
   const Dtype rate = GetLearningRate();
   const auto& ps = net_->learnable_params();
   const auto& fids = net_->failure_learnable_param_ids();
-  const Dtype mom = (Dtype)param_.num("momentum", 0.0);
   const Dtype wd = (Dtype)param_.num("weight_decay", 0.0);
   // only reached when every configured strategy is a ThresholdFailureStrategy
   // and there is at most one (Step's can_fuse); anything else runs unfused
@@ -462,8 +461,9 @@ void Solver<Dtype>::FusedTail() {
   std::vector<Blob<Dtype>*> fi = fmaker_ ? fmaker_->fail_iterations() : std::vector<Blob<Dtype>*>();
   // (cleared with the parameter diffs at the iteration's start, Step)
   unsigned long long* counts = fmaker_ ? fmaker_->device_counts() : nullptr;
-  // one launch for all blobs (rram_fused_update_fail_batched; a net with more
-  // learnable blobs than one launch takes goes one launch per RRAM_MAX_SEGS)
+  // one launch for all blobs (rram_fused_opt_update_fail_batched, SGD one kind
+  // of its kernel like the others; a net with more learnable blobs than one
+  // launch takes goes one launch per RRAM_MAX_SEGS)
   // The flipped kernels of the convolutions whose stride-1 data gradient
   // reads them (Layer::flip_geometry) come out of the same pass, for the next
   // iteration's backward within this Step call (Caffe::step_epoch); not while
@@ -483,18 +483,14 @@ void Solver<Dtype>::FusedTail() {
       }
     }
   std::vector<SyncedMemory*> flipped;
-  // SGD keeps its own entry and kernel; the other types go through
-  // rram_fused_opt_update_fail_batched, whose segment is the same plus h2
-  const bool sgd = kind_ == RRAM_SOLVER_SGD;
   const bool two = kind_ == RRAM_SOLVER_ADADELTA || kind_ == RRAM_SOLVER_ADAM;
-  std::vector<rram_update_seg> segs;
-  std::vector<rram_opt_seg> osegs;
+  std::vector<rram_opt_seg> segs;
   for (int i = 0; i < (int)ps.size(); ++i) {
     int f = -1;
     for (int k = 0; k < (int)fids.size(); ++k)
       if (fids[k] == i) f = k;
     const bool faulty = gm && f >= 0;
-    rram_update_seg sg{};
+    rram_opt_seg sg{};
     sg.w = ps[i]->mutable_gpu_data();
     sg.g = ps[i]->mutable_gpu_diff();
     sg.h = history_[i]->mutable_gpu_data();
@@ -516,35 +512,11 @@ void Solver<Dtype>::FusedTail() {
         flipped.push_back(fl.m);
         break;
       }
-    if (sgd) {
-      segs.push_back(sg);
-      continue;
-    }
-    rram_opt_seg og{};
-    og.w = sg.w;
-    og.g = sg.g;
-    og.h = sg.h;
-    og.endurance = sg.endurance;
-    og.values = sg.values;
-    og.n = sg.n;
-    og.decay = sg.decay;
-    og.local_rate = sg.local_rate;
-    og.thr = sg.thr;
-    og.apply_thr = sg.apply_thr;
-    og.broken_count = sg.broken_count;
-    og.w_flip = sg.w_flip;
-    og.flip_groups = sg.flip_groups;
-    og.flip_cin = sg.flip_cin;
-    og.flip_cout = sg.flip_cout;
-    og.flip_taps = sg.flip_taps;
-    og.h2 = two ? history_[i + ps.size()]->mutable_gpu_data() : nullptr;
-    osegs.push_back(og);
+    if (two) sg.h2 = history_[i + ps.size()]->mutable_gpu_data();
+    segs.push_back(sg);
   }
   for (size_t b = 0; b < segs.size(); b += RRAM_MAX_SEGS)
-    RRAM_CALL(rram_fused_update_fail_batched(segs.data() + b, (int)std::min<size_t>(RRAM_MAX_SEGS, segs.size() - b), mom,
-                                             gm ? gm->decrement : 100.0f, gm ? gm->epsilon : 1e-20f, Caffe::stream()));
-  for (size_t b = 0; b < osegs.size(); b += RRAM_MAX_SEGS)
-    RRAM_CALL(rram_fused_opt_update_fail_batched(osegs.data() + b, (int)std::min<size_t>(RRAM_MAX_SEGS, osegs.size() - b),
+    RRAM_CALL(rram_fused_opt_update_fail_batched(segs.data() + b, (int)std::min<size_t>(RRAM_MAX_SEGS, segs.size() - b),
                                                  kind_, &hyper_, gm ? gm->decrement : 100.0f,
                                                  gm ? gm->epsilon : 1e-20f, Caffe::stream()));
   for (SyncedMemory* m : flipped) m->set_wflip_valid(epoch);

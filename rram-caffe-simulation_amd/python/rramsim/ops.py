@@ -132,14 +132,20 @@ def fused_update_fail(w, g, h, e, v, decay, momentum, lr, apply_thr, thr, decrem
                                           _p(counter), _stream()), "fused_update_fail")
 
 
+def _tail_seg(cls, w, g, h, e, v, decay, lr, apply_thr, thr, counter, flip=None, *h2):
+    """One K.UpdateSeg, or with h2 one K.OptSeg; flip: None or (w_flip, groups, cin, cout, taps)."""
+    flip = flip or (None, 0, 0, 0, 0)
+    for t, nm in ((w, "w"), (g, "g"), (h, "h"), (e, "endurance"), (v, "values"), (flip[0], "w_flip"),
+                  *((t, "h2") for t in h2)):
+        _f32(t, nm)
+    return cls(_p(w), _p(g), _p(h), _p(e), _p(v), w.numel(), decay, lr, thr, int(apply_thr), _p(counter),
+               _p(flip[0]), *flip[1:], *(_p(t) for t in h2))
+
+
 def fused_update_fail_batched(segs, momentum, decrement=100.0, eps=1e-20):
-    """segs: list of (w, g, h, e, v, decay, lr, apply_thr, thr, counter); one launch."""
-    arr = (K.UpdateSeg * len(segs))()
-    for i, (w, g, h, e, v, decay, lr, apply_thr, thr, counter) in enumerate(segs):
-        for t, nm in ((w, "w"), (g, "g"), (h, "h"), (e, "endurance"), (v, "values")):
-            _f32(t, nm)
-        arr[i] = K.UpdateSeg(_p(w), _p(g), _p(h), _p(e), _p(v), w.numel(), decay, lr, thr, int(apply_thr),
-                             _p(counter))
+    """segs: list of (w, g, h, e, v, decay, lr, apply_thr, thr, counter[, (w_flip, groups, cin, cout, taps)]);
+    one launch."""
+    arr = (K.UpdateSeg * len(segs))(*(_tail_seg(K.UpdateSeg, *sg) for sg in segs))
     K.check(_lib().rram_fused_update_fail_batched(arr, len(segs), momentum, decrement, eps, _stream()),
             "fused_update_fail_batched")
 
@@ -183,15 +189,8 @@ def fused_opt_update_fail(kind, hyper, w, g, h, h2, e, v, decay, lr, apply_thr, 
 def fused_opt_update_fail_batched(kind, hyper, segs, decrement=100.0, eps=1e-20):
     """segs: list of (w, g, h, h2, e, v, decay, lr, apply_thr, thr, counter[, (w_flip, groups, cin, cout, taps)]);
     one launch."""
-    arr = (K.OptSeg * len(segs))()
-    for i, sg in enumerate(segs):
-        w, g, h, h2, e, v, decay, lr, apply_thr, thr, counter = sg[:11]
-        for t, nm in ((w, "w"), (g, "g"), (h, "h"), (h2, "h2"), (e, "endurance"), (v, "values")):
-            _f32(t, nm)
-        flip = sg[11] if len(sg) > 11 and sg[11] is not None else (None, 0, 0, 0, 0)
-        _f32(flip[0], "w_flip")
-        arr[i] = K.OptSeg(_p(w), _p(g), _p(h), _p(e), _p(v), w.numel(), decay, lr, thr, int(apply_thr), _p(counter),
-                          _p(flip[0]), *flip[1:], _p(h2))
+    arr = (K.OptSeg * len(segs))(*(_tail_seg(K.OptSeg, *sg[:3], *sg[4:11], sg[11] if len(sg) > 11 else None, sg[3])
+                                   for sg in segs))
     K.check(_lib().rram_fused_opt_update_fail_batched(arr, len(segs), int(kind), C.byref(hyper), decrement, eps,
                                                       _stream()), "fused_opt_update_fail_batched")
 

@@ -6,8 +6,10 @@ each solver type, all in one process.
 Per type: a warm-up, `--repeats` timed repeats of `--iters` iterations each
 (device synchronised around each), the median ms per iteration and the spread
 ((max - min) / median) of the repeats.  Then the tail timer: the one-launch
-fused tail alone (rram_fused_update_fail_batched for SGD,
-rram_fused_opt_update_fail_batched for the others) on scratch blobs of the
+fused tail alone (one kernel for all types; SGD goes in through
+rram_fused_update_fail_batched, so that a build from before the other types
+is measured through the same entry, the others through
+rram_fused_opt_update_fail_batched) on scratch blobs of the
 net's own learnable shapes and fault state, between two device events, and
 the bytes it moves (9 floats per faultable element, 5 per other element, 2
 more per element with a second history), so its GB/s.  One JSON line per

@@ -218,7 +218,8 @@ def test_batched_equals_per_blob(device, kind):
     blob: sizes straddling the 2048-element chunk, a 216-element convolution
     blob with its flipped copy, one segment without fault state, two segments
     sharing one counter, per-segment decay / rate / threshold.  For SGD the
-    new entry also == rram_fused_update_fail_batched."""
+    entry also == rram_fused_update_fail_batched (the same kernel behind the
+    narrower segment, the convolution blob's flipped copy included)."""
     import torch
     from rramsim import _kernels as K
     from rramsim import ops
@@ -241,7 +242,7 @@ def test_batched_equals_per_blob(device, kind):
         thr = _calibrated_threshold(kind, w, g, h, h2, hyper, lr, decay)
         blobs.append((w, g, h, h2, e if faulty else None, v if faulty else None, decay, lr, faulty, thr))
     cnt_b, cnt_u, cnt_s = (ops.counters(len(sizes), device) for _ in range(3))
-    flip_b = torch.zeros(sizes[conv], dtype=torch.float32, device=device)
+    flip_b, flip_s = (torch.zeros(sizes[conv], dtype=torch.float32, device=device) for _ in range(2))
     segs, sgd_segs, outs_b, outs_u, outs_s = [], [], [], [], []
     for k, (w, g, h, h2, e, v, decay, lr, faulty, thr) in enumerate(blobs):
         mk = lambda: [T(x, device) if x is not None else None for x in (w, g, h, h2, e, v)]  # noqa: E731
@@ -251,7 +252,8 @@ def test_batched_equals_per_blob(device, kind):
         segs.append((*tb, decay, float(lr), faulty, float(thr), cb,
                      (flip_b, G, cin, cout, taps) if k == conv else None))
         ops.fused_opt_update_fail(K.SOLVER_KINDS[kind], hy, *tu, decay, float(lr), faulty, float(thr), counter=cu)
-        sgd_segs.append((ts[0], ts[1], ts[2], ts[4], ts[5], decay, float(lr), faulty, float(thr), cs))
+        sgd_segs.append((ts[0], ts[1], ts[2], ts[4], ts[5], decay, float(lr), faulty, float(thr), cs,
+                         (flip_s, G, cin, cout, taps) if k == conv else None))
         outs_b.append(tb)
         outs_u.append(tu)
         outs_s.append(ts)
@@ -278,3 +280,4 @@ def test_batched_equals_per_blob(device, kind):
                 if tb[j] is not None:
                     assert bits_equal(N(tb[j]), N(ts[j])), (k, j)
         assert (N(cnt_b) == N(cnt_s)).all()
+        assert bits_equal(N(flip_s), _np_flip(N(outs_s[conv][0]), G, cin, cout, taps))

@@ -1,8 +1,8 @@
 """Fault-aware training with every solver type: LeNet (two convolutions, two
 InnerProducts), batch 8, a gaussian failure pattern and the threshold strategy.
 
-The one-launch fused tail (rram_fused_opt_update_fail_batched; SGD keeps
-rram_fused_update_fail_batched) must leave the bits of the reference order
+The one-launch fused tail (rram_fused_opt_update_fail_batched, SGD one kind of
+its kernel like the others) must leave the bits of the reference order
 ComputeUpdate -> ApplyStrategy -> ApplyUpdate -> Fail (solver.cpp:299-305) run
 as separate kernels; the types must differ from one another; a remapping
 strategy takes the unfused path; hipGraph replay equals eager, Adam staying
