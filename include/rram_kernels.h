@@ -496,6 +496,44 @@ int rram_conv_octet_plan(const rram_conv_desc* d, int* plan);
  * per line, without the /kind suffix. */
 int rram_conv_fwd_kernel_id(const rram_conv_desc* d, int x_align16, char* out, size_t cap);
 int rram_conv_fwd_kernel_list(char* out, size_t cap);
+/* Which kernels of the fp32-MFMA engine an entry point would launch right now
+ * (no reference counterpart: the reference's engine is cuBLAS SGEMM; host
+ * only, no device work, nothing allocated).  Each query runs the entry
+ * point's own planning code with its launches recorded instead of issued, and
+ * returns one line per launch, in launch order, in snprintf style as above:
+ *   gemm<AM,BM,OM,KB;RxC>/sS   k_gemm: operand modes (KC KCV KCU RC NCHW |
+ *                              KC KCV RC CONV CONVT CONVT64 IM2T NCHWT), output
+ *                              mode (ROWMAJOR NCHW), K-tile depth, R x C tile,
+ *                              S K-splits (1: none); then " MxNxK", the
+ *                              product's extents (also after gemm2, patch_f32)
+ *   gemm2<KCV,KCV,ROWMAJOR,3>/sS   the 3-stage NT kernel
+ *   patch_pack, patch_f32<KH,CPH,MI,PD>   fp32 patch convolution and its weight pack
+ *   gemv, gemv_groups, im2col, im2col4, col2im
+ *   reduce, reduce_groups, reduce_nchw, reduce_dwdb, reduce_wave   split-K reduces
+ *   aux:NAME                   an elementwise helper outside the engine (bias_bwd,
+ *                              bias_bwd_part, bias_bwd_reduce, bias_add, relu, flip_kernel)
+ *   x6:ID                      the bf16x6 engine takes the call (one line)
+ * *_align16: whether that operand is 16-byte aligned (else 4); workspaces and
+ * outputs count as aligned.  ws_bytes = 0 means no workspace.
+ *   rram_gemm_kernel_ids          rram_gemm_f32_ex (beta_zero: beta == 0)
+ *   rram_ip_fwd_kernel_ids        rram_ip_fwd (bias / relu: given or not)
+ *   rram_ip_bwd_kernel_ids        rram_ip_bwd (want_*: that gradient is not NULL)
+ *   rram_ip_fwd_groups_kernel_ids rram_ip_fwd_groups
+ *   rram_conv_fwd_kernel_ids      rram_conv2d_fwd
+ *   rram_conv_bwd_kernel_ids      rram_conv2d_bwd_ex (have_w_flipped: w_flipped given)
+ *   rram_f32_kernel_list          every instantiated kernel of the above, without /sS */
+int rram_gemm_kernel_ids(int trans_a, int trans_b, int M, int N, int K, int lda, int ldb, int a_align16,
+                         int b_align16, int beta_zero, size_t ws_bytes, char* out, size_t cap);
+int rram_ip_fwd_kernel_ids(int M, int N, int K, int transpose, int x_align16, int w_align16, int bias, int relu,
+                           size_t ws_bytes, char* out, size_t cap);
+int rram_ip_bwd_kernel_ids(int M, int N, int K, int transpose, int want_dw, int want_db, int want_dx, int align16,
+                           char* out, size_t cap);
+int rram_ip_fwd_groups_kernel_ids(int G, int M, int N, int K, int transpose, int64_t w_group_stride, int align16,
+                                  size_t ws_bytes, char* out, size_t cap);
+int rram_conv_fwd_kernel_ids(const rram_conv_desc* d, int x_align16, int w_align16, char* out, size_t cap);
+int rram_conv_bwd_kernel_ids(const rram_conv_desc* d, int want_dw, int want_db, int want_dx, size_t ws_bytes,
+                             int have_w_flipped, int w_align16, char* out, size_t cap);
+int rram_f32_kernel_list(char* out, size_t cap);
 /* The fp32 engine's implicit-GEMM forward picks its split-K count from num.
  * num > 0 pins that choice to the plan of a batch of `num` images for every
  * later forward of a larger batch (0: each call's own num, the default), so

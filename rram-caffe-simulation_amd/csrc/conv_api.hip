@@ -37,6 +37,7 @@ int release_conv_tables();
 std::atomic<uint64_t>& scratch_gen();
 int pack_octets(const float* x, void* oct, int num, int C, int HWi, hipStream_t s);
 std::atomic<int>& f32_engine();
+std::string f32_kernel_list();
 
 namespace {
 
@@ -369,11 +370,13 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
       float* part = static_cast<float*>(ws);
       const int per = (d.num + S - 1) / S;
       const int Sx = (d.num + per - 1) / per;
-      hipLaunchKernelGGL(k_bias_bwd_part, dim3(d.num_output, Sx), dim3(256), 0, s, dy, part, d.num, d.num_output,
-                         HoWo, per);
-      hipLaunchKernelGGL(k_bias_bwd_reduce, dim3(d.num_output), dim3(64), 0, s, part, db,
-                         d.num_output, Sx);
-    } else {
+      if (!plan_note("aux:bias_bwd_part\naux:bias_bwd_reduce")) {
+        hipLaunchKernelGGL(k_bias_bwd_part, dim3(d.num_output, Sx), dim3(256), 0, s, dy, part, d.num, d.num_output,
+                           HoWo, per);
+        hipLaunchKernelGGL(k_bias_bwd_reduce, dim3(d.num_output), dim3(64), 0, s, part, db,
+                           d.num_output, Sx);
+      }
+    } else if (!plan_note("aux:bias_bwd")) {
       hipLaunchKernelGGL(k_bias_bwd, dim3(d.num_output), dim3(256), 0, s, dy, db, d.num, d.num_output, HoWo);
     }
     rc = launch_status("conv bias bwd");
@@ -402,7 +405,8 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
     if (wt == nullptr) {
       float* wf = static_cast<float*>(ws);
       const int64_t n = (int64_t)d.channels * cout_g * T;
-      hipLaunchKernelGGL(k_flip_kernel, dim3(stream_blocks(n)), dim3(256), 0, s, w, wf, G, cin_g, cout_g, T);
+      if (!plan_note("aux:flip_kernel"))
+        hipLaunchKernelGGL(k_flip_kernel, dim3(stream_blocks(n)), dim3(256), 0, s, w, wf, G, cin_g, cout_g, T);
       r = launch_status("conv bwd kernel flip");
       if (r) return r;
       wt = wf;
@@ -488,6 +492,11 @@ int rram_ip_fwd(const float* x, const float* w, const float* bias, float* y, int
     // does the transposed product, which this build follows: Appendix Q15.)
     int rc = gemv_core(0, N, K, 1.0f, w, x, 0.0f, y, as_stream(s));
     if (rc) return rc;
+    if (planning()) {  // the two elementwise passes launch outside the engine's files
+      if (bias && N > 0) plan_note("aux:bias_add");
+      if (relu && N > 0) plan_note("aux:relu");
+      return RRAM_OK;
+    }
     if (bias) {
       rc = rram_bias_add(y, bias, 1, N, 1, s);
       if (rc) return rc;
@@ -553,7 +562,7 @@ int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw, floa
   if (db) {
     // db[n] += sum_m dY[m][n]  (the reference's gemv against bias_multiplier_)
     if (M > 0 && N > 0) {
-      hipLaunchKernelGGL(k_bias_bwd, dim3(N), dim3(256), 0, s, dy, db, M, N, 1);
+      if (!plan_note("aux:bias_bwd")) hipLaunchKernelGGL(k_bias_bwd, dim3(N), dim3(256), 0, s, dy, db, M, N, 1);
       rc = launch_status("ip bias bwd");
       if (rc) return rc;
     }
@@ -585,5 +594,71 @@ int rram_bias_bwd(const float* dy, float* db, int num, int C, int inner, rram_st
   hipLaunchKernelGGL(k_bias_bwd, dim3(C), dim3(256), 0, as_stream(s), dy, db, num, C, inner);
   return launch_status("bias_bwd");
 }
+
+// ---- which kernels the fp32 engine's entry points launch (host only) ----
+// Each query opens a PlanScope and calls the entry point itself with operand
+// pointers that carry only the stated alignment, so the ids come from the
+// launch paths' own planning code.
+namespace {
+// a 256-byte aligned address (the allocators' alignment), or 4 bytes past one
+float* plan_ptr(int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); }
+int plan_result(int rc, const PlanScope& sc, char* out, size_t cap) { return rc ? rc : copy_text(sc.text, out, cap); }
+}  // namespace
+
+int rram_gemm_kernel_ids(int trans_a, int trans_b, int M, int N, int K, int lda, int ldb, int a_align16,
+                         int b_align16, int beta_zero, size_t ws_bytes, char* out, size_t cap) {
+  PlanScope sc;
+  const int ldc = N > 0 ? N : 1;
+  const int rc = rram_gemm_f32_ex(trans_a, trans_b, M, N, K, 1.0f, plan_ptr(a_align16), lda, plan_ptr(b_align16), ldb,
+                                  beta_zero ? 0.0f : 1.0f, plan_ptr(1), ldc, nullptr, RRAM_BIAS_NONE, 0,
+                                  ws_bytes ? plan_ptr(1) : nullptr, ws_bytes, nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_ip_fwd_kernel_ids(int M, int N, int K, int transpose, int x_align16, int w_align16, int bias, int relu,
+                           size_t ws_bytes, char* out, size_t cap) {
+  PlanScope sc;
+  const int rc = rram_ip_fwd(plan_ptr(x_align16), plan_ptr(w_align16), bias ? plan_ptr(1) : nullptr, plan_ptr(1), M, N,
+                             K, transpose, relu, ws_bytes ? plan_ptr(1) : nullptr, ws_bytes, nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_ip_bwd_kernel_ids(int M, int N, int K, int transpose, int want_dw, int want_db, int want_dx, int align16,
+                           char* out, size_t cap) {
+  PlanScope sc;
+  float* p = plan_ptr(align16);
+  const int rc = rram_ip_bwd(p, p, p, want_dw ? p : nullptr, want_db ? p : nullptr, want_dx ? p : nullptr, M, N, K,
+                             transpose, nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_ip_fwd_groups_kernel_ids(int G, int M, int N, int K, int transpose, int64_t w_group_stride, int align16,
+                                  size_t ws_bytes, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = plan_ptr(align16);
+  const int rc = rram_ip_fwd_groups(p, p, w_group_stride, nullptr, 0, p, G, M, N, K, transpose, 0,
+                                    ws_bytes ? plan_ptr(1) : nullptr, ws_bytes, nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_conv_fwd_kernel_ids(const rram_conv_desc* d, int x_align16, int w_align16, char* out, size_t cap) {
+  RRAM_REQUIRE(d != nullptr, "kernel id query: desc is NULL");
+  PlanScope sc;
+  const int rc = rram_conv2d_fwd(d, plan_ptr(x_align16), plan_ptr(w_align16), nullptr, plan_ptr(1), 0, nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_conv_bwd_kernel_ids(const rram_conv_desc* d, int want_dw, int want_db, int want_dx, size_t ws_bytes,
+                             int have_w_flipped, int w_align16, char* out, size_t cap) {
+  RRAM_REQUIRE(d != nullptr, "kernel id query: desc is NULL");
+  PlanScope sc;
+  float* p = plan_ptr(1);
+  const int rc = rram_conv2d_bwd_ex(d, p, plan_ptr(w_align16), have_w_flipped ? p : nullptr, p, want_dw ? p : nullptr,
+                                    want_db ? p : nullptr, want_dx ? p : nullptr, ws_bytes ? p : nullptr, ws_bytes,
+                                    nullptr);
+  return plan_result(rc, sc, out, cap);
+}
+
+int rram_f32_kernel_list(char* out, size_t cap) { return copy_text(rram::f32_kernel_list(), out, cap); }
 
 }  // extern "C"

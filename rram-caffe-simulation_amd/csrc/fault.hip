@@ -785,7 +785,24 @@ void set_error(const char* fmt, ...) {
 void clear_error() { g_err.clear(); }
 const char* last_error_cstr() { return g_err.c_str(); }
 
+static thread_local std::string* g_plan = nullptr;
+bool planning() { return g_plan != nullptr; }
+bool plan_note(const char* fmt, ...) {
+  if (g_plan == nullptr) return false;
+  char buf[160];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  *g_plan += buf;
+  *g_plan += '\n';
+  return true;
+}
+PlanScope::PlanScope() { g_plan = &text; }
+PlanScope::~PlanScope() { g_plan = nullptr; }
+
 int launch_status(const char* what) {
+  if (g_plan != nullptr) return RRAM_OK;  // nothing was launched
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s launch: %s", what, hipGetErrorString(e));

@@ -1352,14 +1352,50 @@ __global__ void __launch_bounds__(256)
 }
 
 
+// Text ids of the kernel-id queries (rram_gemm_kernel_ids; one line per launch)
+const char* mode_name(int m) {
+  static const char* const n[] = {"KC", "RC", "CONV", "NCHW", "NCHWT", "KCV", "CONVT", "CONVT64", "KCU", "IM2T"};
+  return n[m];
+}
+std::string gemm_id(int am, int bm, int om, int kb, int rows, int cols, int split) {
+  char b[96];
+  snprintf(b, sizeof b, "gemm<%s,%s,%s,%d;%dx%d>", mode_name(am), mode_name(bm), om == OUT_NCHW ? "NCHW" : "ROWMAJOR",
+           kb, rows, cols);
+  std::string t = b;
+  if (split > 0) t += "/s" + std::to_string(split);  // 0: the instantiation's name (rram_f32_kernel_list)
+  return t;
+}
+
+// The tiles (rows x columns) launch<>() may instantiate per K-tile depth:
+// rram_f32_kernel_list prints these, and launch_cfg refuses to compile a tile
+// that is not listed here.
+constexpr int kTiles32[][2] = {{32, 128}, {64, 64}, {64, 128}, {96, 128}, {128, 128}, {192, 128}};
+constexpr int kTiles16[][2] = {{64, 64}, {64, 128}, {128, 128}, {192, 128}, {128, 256}};
+template <int KB>
+constexpr bool tile_listed(int rows, int cols) {
+  if (KB == 32) {
+    for (const auto& t : kTiles32)
+      if (t[0] == rows && t[1] == cols) return true;
+  } else {
+    for (const auto& t : kTiles16)
+      if (t[0] == rows && t[1] == cols) return true;
+  }
+  return false;
+}
+
 template <int WM, int WN, int MI, int NI, int AM, int BMODE, int OM, int KB>
 int launch_cfg(Params P, int gz, hipStream_t s) {
   constexpr int BMr = WM * MI * 32, BNr = WN * NI * 32;
+  static_assert(tile_listed<KB>(BMr, BNr), "add the tile to kTiles32 / kTiles16");
   P.tiles_m = (P.M + BMr - 1) / BMr;
   P.tiles_n = (P.N + BNr - 1) / BNr;
   P.tiles_z = gz;
   const int64_t nwg = (int64_t)P.tiles_m * P.tiles_n * gz;
   RRAM_REQUIRE(nwg < (1ll << 31), "gemm: grid too large");
+  if (planning()) {
+    plan_note("%s %dx%dx%d", gemm_id(AM, BMODE, OM, KB, BMr, BNr, P.split).c_str(), P.M, P.N, P.K);
+    return RRAM_OK;
+  }
   hipLaunchKernelGGL((k_gemm<WM, WN, MI, NI, AM, BMODE, OM, KB>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, P);
   return launch_status("gemm");
 }
@@ -1402,8 +1438,10 @@ int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
   // conv3 (507 such tiles, one round) 0.70 -> 0.69 ms is within noise, and
   // conv4 / conv5 / conv1 (fewer tiles or M % 128 != 0) are slower, so they
   // keep the policy below.
-  if (KB == 16 && P.M % 128 == 0 && (int64_t)(P.M / 128) * ((P.N + 255) / 256) * pz >= 1024)
-    return launch_cfg<2, 2, 2, 4, AM, BMODE, OM, KB>(P, gz, s);
+  if constexpr (KB == 16) {
+    if (P.M % 128 == 0 && (int64_t)(P.M / 128) * ((P.N + 255) / 256) * pz >= 1024)
+      return launch_cfg<2, 2, 2, 4, AM, BMODE, OM, KB>(P, gz, s);
+  }
   const int64_t ntn = (P.N + 127) / 128;
   const int cands[4] = {128, 192, 96, 64};  // ties keep 128 (2 blocks per CU)
   int best = 0;
@@ -1438,6 +1476,7 @@ int launch2(Params P, int gz, hipStream_t s) {
   P.tiles_z = gz;
   const int64_t nwg = (int64_t)P.tiles_m * P.tiles_n * gz;
   RRAM_REQUIRE(nwg < (1ll << 31), "gemm: grid too large");
+  if (plan_note("gemm2<KCV,KCV,ROWMAJOR,3>/s%d %dx%dx%d", P.split, P.M, P.N, P.K)) return RRAM_OK;
   hipLaunchKernelGGL((k_gemm2<AM, BMODE, OM, 3>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, P);
   return launch_status("gemm2");
 }
@@ -1466,45 +1505,35 @@ int conv_kb(int K) {
   return K >= 1024 ? 16 : 32;
 }
 
+// The instantiated (A mode, B mode, output mode) combinations of k_gemm: the
+// implicit-GEMM convolution forwards at 16-deep K-tiles (conv_kb), and every
+// combination at 32-deep ones.  dispatch() and rram_f32_kernel_list expand
+// the same lists.
+#define RRAM_GEMM_LIST16(X)                                                                   \
+  X(KC, CONV, OUT_NCHW) X(KCV, CONV, OUT_NCHW)                                                \
+  X(KC, CONVT, OUT_NCHW) X(KCV, CONVT, OUT_NCHW) X(KCU, CONVT, OUT_NCHW)                      \
+  X(KC, CONVT64, OUT_NCHW) X(KCV, CONVT64, OUT_NCHW)
+#define RRAM_GEMM_LIST32(X)                                                                   \
+  X(KC, KC, OUT_ROWMAJOR) X(KCV, KC, OUT_ROWMAJOR) X(KC, KCV, OUT_ROWMAJOR) X(KCV, KCV, OUT_ROWMAJOR) \
+  X(KC, RC, OUT_ROWMAJOR) X(KCV, RC, OUT_ROWMAJOR)                                            \
+  X(RC, KC, OUT_ROWMAJOR) X(RC, KCV, OUT_ROWMAJOR) X(RC, RC, OUT_ROWMAJOR)                    \
+  X(KC, CONV, OUT_NCHW) X(KCV, CONV, OUT_NCHW)                                                \
+  X(KC, CONVT, OUT_NCHW) X(KCV, CONVT, OUT_NCHW) X(KCU, CONVT, OUT_NCHW)                      \
+  X(KC, CONVT64, OUT_NCHW) X(KCV, CONVT64, OUT_NCHW)                                          \
+  X(NCHW, KC, OUT_ROWMAJOR) X(NCHW, KCV, OUT_ROWMAJOR) X(NCHW, IM2T, OUT_ROWMAJOR)            \
+  X(RC, NCHWT, OUT_ROWMAJOR)
+
 int dispatch(int am, int bm, int om, const Params& P, int gz, hipStream_t s, bool force_big = false, int pz = 0) {
   if (gemm2_ok(am, bm, P)) {
     if (om == OUT_ROWMAJOR) return launch2<KCV, KCV, OUT_ROWMAJOR>(P, gz, s);
   }
-  if (bm == CONV && om == OUT_NCHW && conv_kb(P.K) == 16) {
-    if (am == KC) return launch<KC, CONV, OUT_NCHW, 16>(P, gz, s, force_big);
-    if (am == KCV) return launch<KCV, CONV, OUT_NCHW, 16>(P, gz, s, force_big);
-  }
-  if (bm == CONVT && om == OUT_NCHW && conv_kb(P.K) == 16) {
-    if (am == KC) return launch<KC, CONVT, OUT_NCHW, 16>(P, gz, s, force_big);
-    if (am == KCV) return launch<KCV, CONVT, OUT_NCHW, 16>(P, gz, s, force_big);
-    if (am == KCU) return launch<KCU, CONVT, OUT_NCHW, 16>(P, gz, s, force_big);
-  }
-  if (bm == CONVT64 && om == OUT_NCHW && conv_kb(P.K) == 16) {
-    if (am == KC) return launch<KC, CONVT64, OUT_NCHW, 16>(P, gz, s, force_big);
-    if (am == KCV) return launch<KCV, CONVT64, OUT_NCHW, 16>(P, gz, s, force_big);
-  }
+#define RRAM_D(A_, B_, O_) \
+  if (am == A_ && bm == B_ && om == O_ && conv_kb(P.K) == 16) return launch<A_, B_, O_, 16>(P, gz, s, force_big);
+  RRAM_GEMM_LIST16(RRAM_D)
+#undef RRAM_D
 #define RRAM_D(A_, B_, O_) \
   if (am == A_ && bm == B_ && om == O_) return launch<A_, B_, O_, 32>(P, gz, s, force_big, pz);
-  RRAM_D(KC, KC, OUT_ROWMAJOR)
-  RRAM_D(KCV, KC, OUT_ROWMAJOR)
-  RRAM_D(KC, KCV, OUT_ROWMAJOR)
-  RRAM_D(KCV, KCV, OUT_ROWMAJOR)
-  RRAM_D(KC, RC, OUT_ROWMAJOR)
-  RRAM_D(KCV, RC, OUT_ROWMAJOR)
-  RRAM_D(RC, KC, OUT_ROWMAJOR)
-  RRAM_D(RC, KCV, OUT_ROWMAJOR)
-  RRAM_D(RC, RC, OUT_ROWMAJOR)
-  RRAM_D(KC, CONV, OUT_NCHW)
-  RRAM_D(KCV, CONV, OUT_NCHW)
-  RRAM_D(KC, CONVT, OUT_NCHW)
-  RRAM_D(KCV, CONVT, OUT_NCHW)
-  RRAM_D(KCU, CONVT, OUT_NCHW)
-  RRAM_D(KC, CONVT64, OUT_NCHW)
-  RRAM_D(KCV, CONVT64, OUT_NCHW)
-  RRAM_D(NCHW, KC, OUT_ROWMAJOR)
-  RRAM_D(NCHW, KCV, OUT_ROWMAJOR)
-  RRAM_D(NCHW, IM2T, OUT_ROWMAJOR)
-  RRAM_D(RC, NCHWT, OUT_ROWMAJOR)
+  RRAM_GEMM_LIST32(RRAM_D)
 #undef RRAM_D
   set_error("gemm: unsupported operand combination %d/%d/%d", am, bm, om);
   return RRAM_EUNSUPPORTED;
@@ -1657,6 +1686,7 @@ int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const 
     P.ws = static_cast<float*>(ws);
     int rc = dispatch(am, bm, OUT_ROWMAJOR, P, split, s, true);
     if (rc) return rc;
+    if (plan_note("reduce")) return RRAM_OK;
     hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s,
                        P.ws, split, M, N, P.e);
     return launch_status("gemm splitk reduce");
@@ -1760,6 +1790,7 @@ int gemm_groups_core(int G, int trans_b, int M, int N, int K, const float* A, in
     P.zgroups = G;
     int rc = dispatch(am, bm, OUT_ROWMAJOR, P, G * split, s, true, split);
     if (rc) return rc;
+    if (plan_note("reduce_groups")) return 1;
     hipLaunchKernelGGL(k_splitk_reduce_groups, dim3(stream_blocks((int64_t)G * M * N)), dim3(256), 0, s, P.ws, split, M,
                        N, P.e, G, grp_c, grp_bias);
     rc = launch_status("gemm groups splitk reduce");
@@ -1805,6 +1836,7 @@ int gemv_groups_core(int G, int N, int K, const float* W, int64_t grp_w, const f
   const int64_t outs = (int64_t)G * N;
   RRAM_REQUIRE(outs < (1ll << 31), "gemv groups: too many outputs");
   const int blocks = static_cast<int>(std::min<int64_t>((outs + 3) / 4, 4096));
+  if (plan_note("gemv_groups")) return RRAM_OK;
   hipLaunchKernelGGL(k_gemv_groups, dim3(blocks), dim3(256), 0, s, G, N, K, W, grp_w, x, bias, grp_bias, relu, y);
   return launch_status("gemv groups");
 }
@@ -1856,6 +1888,7 @@ int launch_patch(Params P, const float* wpack, int PW, int CS, int gz, hipStream
   P.tiles_z = gz;
   const int64_t nwg = (int64_t)P.tiles_m * P.tiles_n * gz;
   RRAM_REQUIRE(nwg < (1ll << 31), "conv: grid too large");
+  if (plan_note("patch_f32<%d,%d,%d,%d> %dx%dx%d", KH, CPH, MI, PD, P.M, P.N, P.K)) return RRAM_OK;
   bool done = false;
   if constexpr (two_fit) {
     if (nst == 2) {
@@ -1874,6 +1907,10 @@ int launch_patch(Params P, const float* wpack, int PW, int CS, int gz, hipStream
 // planes hold >= 128 positions.  Returns 1 when it ran, 0 when the shape is
 // not covered (the caller falls back to the implicit-im2col GEMM), < 0 on
 // error.
+// the instantiated k_conv_patch forms (KH = KW, CPH, MI, PD)
+#define RRAM_PATCH_F32_LIST(X)                                                                  \
+  X(3, 2, 2, 4) X(3, 2, 2, 6) X(3, 2, 2, 8) X(3, 2, 3, 4) X(3, 2, 3, 6) X(3, 2, 3, 8)           \
+  X(5, 1, 2, 4) X(5, 1, 2, 6) X(5, 1, 2, 8) X(5, 1, 3, 4)
 int conv_patch_fwd(const rram_conv_desc* d, const float* w, Params& P, hipStream_t s) {
   const int KH = d->kernel_h, KW = d->kernel_w;
   if (d->stride_h != 1 || d->stride_w != 1 || d->dilation_h != 1 || d->dilation_w != 1) return 0;
@@ -1915,16 +1952,19 @@ int conv_patch_fwd(const rram_conv_desc* d, const float* w, Params& P, hipStream
   const int tiles_m = mt / BMc, ktiles = Cg / (2 * CPH);
   const int64_t total = (int64_t)G * tiles_m * ktiles * BMc * RL;
   RRAM_REQUIRE(total * 4 < (1ll << 31), "conv: packed weights must be < 2 GiB");
-  float* wp = pack_buffer(static_cast<size_t>(total), s);
-  RRAM_REQUIRE(wp != nullptr, "conv: packed-weight buffer allocation failed");
-  hipLaunchKernelGGL(k_conv_patch_pack, dim3(stream_blocks(total)), dim3(256), 0, s, w, wp, G, M, Cg, T, CPH, HP, RL,
-                     BMc, tiles_m, ktiles, total);
-  int rc = launch_status("conv weight pack");
-  if (rc) return rc;
+  float* wp = nullptr;
+  int rc = 0;
+  if (!plan_note("patch_pack")) {
+    wp = pack_buffer(static_cast<size_t>(total), s);
+    RRAM_REQUIRE(wp != nullptr, "conv: packed-weight buffer allocation failed");
+    hipLaunchKernelGGL(k_conv_patch_pack, dim3(stream_blocks(total)), dim3(256), 0, s, w, wp, G, M, Cg, T, CPH, HP, RL,
+                       BMc, tiles_m, ktiles, total);
+    rc = launch_status("conv weight pack");
+    if (rc) return rc;
+  }
 #define RRAM_P(KH_, CPH_, MI_, PD_) \
   if (KH == KH_ && MI == MI_ && PD == PD_) rc = launch_patch<KH_, KH_, CPH_, MI_, PD_>(P, wp, PW, CS, G, s); else
-  RRAM_P(3, 2, 2, 4) RRAM_P(3, 2, 2, 6) RRAM_P(3, 2, 2, 8) RRAM_P(3, 2, 3, 4) RRAM_P(3, 2, 3, 6) RRAM_P(3, 2, 3, 8)
-  RRAM_P(5, 1, 2, 4) RRAM_P(5, 1, 2, 6) RRAM_P(5, 1, 2, 8) RRAM_P(5, 1, 3, 4)
+  RRAM_PATCH_F32_LIST(RRAM_P)
   return 0;
 #undef RRAM_P
   return rc ? rc : 1;
@@ -2013,9 +2053,9 @@ int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const
   int bmode = CONV;
   if ((!padded || taps <= 63) &&
       (int64_t)cin_g * d->height * d->width * 4 < (1ll << 31)) {
-    cv.tbl = conv_table(cv, K, padded, wide, s);
+    if (!planning()) cv.tbl = conv_table(cv, K, padded, wide, s);
     cv.taps = padded ? taps : 0;
-    if (cv.tbl) bmode = wide ? CONVT64 : CONVT;
+    if (cv.tbl || planning()) bmode = wide ? CONVT64 : CONVT;
   }
   // A: 16-byte loads when the rows are 16-byte aligned; else (K % 4 != 0) the
   // unaligned raw-buffer form for the table gather
@@ -2033,13 +2073,14 @@ int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const
       const int kb = conv_kb(K);
       const int kc = ((K + split - 1) / split + kb - 1) / kb * kb;
       const int sp = (K + kc - 1) / kc;
-      float* ws = stream_buffer(1, (size_t)sp * P.M * P.N, s);
-      RRAM_REQUIRE(ws != nullptr, "conv2d_fwd: split-K buffer allocation failed");
+      float* ws = planning() ? nullptr : stream_buffer(1, (size_t)sp * P.M * P.N, s);
+      RRAM_REQUIRE(ws != nullptr || planning(), "conv2d_fwd: split-K buffer allocation failed");
       P.split = sp;
       P.k_chunk = kc;
       P.ws = ws;
       int rc = dispatch(amode, bmode, OUT_NCHW, P, sp, s);
       if (rc) return rc;
+      if (plan_note("reduce_nchw")) return RRAM_OK;
       hipLaunchKernelGGL(k_splitk_reduce_nchw, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, ws, sp, P.M,
                          P.N, P.e);
       return launch_status("conv fwd split-K reduce");
@@ -2047,6 +2088,10 @@ int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const
   }
   return dispatch(amode, bmode, OUT_NCHW, P, g, s);
 }
+
+// the weight gradient's partials are summed by k_splitk_reduce_wave (one wave
+// per output) from this many splits on
+bool reduce_by_wave(int split) { return split >= 32; }
 
 // Split-K factor of the weight-gradient GEMM: M = Cout/g and N = Cin/g*kh*kw
 // are small while K = images*Ho*Wo is long (CIFAR conv1: 32 x 75 x 102400),
@@ -2116,8 +2161,8 @@ int conv_bwd_weight_im2t(const rram_conv_desc* d, const float* x, const float* d
   cv.howo = make_fastdiv(HoWo);
   cv.wo_div = make_fastdiv(d->out_w);
   cv.chw = (int64_t)d->channels * d->height * d->width;
-  cv.tbl = im2t_table(cv, K, db != nullptr, 256, s);
-  RRAM_REQUIRE(cv.tbl != nullptr, "conv bwd weight: gather table allocation failed");
+  if (!planning()) cv.tbl = im2t_table(cv, K, db != nullptr, 256, s);
+  RRAM_REQUIRE(cv.tbl != nullptr || planning(), "conv bwd weight: gather table allocation failed");
   const int N = K + (db ? 1 : 0);
   for (int gi = 0; gi < g; ++gi) {
     Params P{};
@@ -2143,7 +2188,8 @@ int conv_bwd_weight_im2t(const rram_conv_desc* d, const float* x, const float* d
     P.ws = static_cast<float*>(part);
     int rc = dispatch(NCHW, IM2T, OUT_ROWMAJOR, P, split, s, true);
     if (rc) return rc;
-    if (split >= 32)
+    if (plan_note(reduce_by_wave(split) ? "reduce_wave" : db ? "reduce_dwdb" : "reduce")) continue;
+    if (reduce_by_wave(split))
       hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256), 0,
                          s, P.ws, split, P.M, K, P.N, P.e.C, db);
     else if (db)
@@ -2188,7 +2234,8 @@ int conv_bwd_weight_core(const rram_conv_desc* d, int nimg, const float* dy, con
     P.ws = static_cast<float*>(part);
     int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, split, s, true);
     if (rc) return rc;
-    if (split >= 32)
+    if (plan_note(reduce_by_wave(split) ? "reduce_wave" : "reduce_dwdb")) return RRAM_OK;
+    if (reduce_by_wave(split))
       hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256), 0,
                          s, P.ws, split, P.M, K, P.N, dw, db);
     else
@@ -2221,7 +2268,8 @@ int conv_bwd_weight_core(const rram_conv_desc* d, int nimg, const float* dy, con
       int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, split, s, true);
       if (rc) return rc;
       // dw += sum of the partials (beta = 1), fixed summation order
-      if (split >= 32)  // (dw of group gi: P.e.C)
+      if (plan_note(reduce_by_wave(split) ? "reduce_wave" : "reduce")) continue;
+      if (reduce_by_wave(split))  // (dw of group gi: P.e.C)
         hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256),
                            0, s, P.ws, split, P.M, P.N, P.N, P.e.C, nullptr);
       else
@@ -2273,6 +2321,7 @@ int im2col_core(const float* im, int64_t im_img, int nimg, const rram_conv_desc*
                "im2col: more than 2^31 positions / input elements or 65535 rows is not supported");
   if ((d->out_h * d->out_w) % 4 == 0 && ldcol % 4 == 0 && (reinterpret_cast<uintptr_t>(col) & 15u) == 0) {
     const int gx4 = static_cast<int>(std::min<int64_t>((P / 4 + 255) / 256, 64));
+    if (plan_note("im2col4")) return RRAM_OK;
     hipLaunchKernelGGL(k_im2col4, dim3(gx4, rows), dim3(256), 0, s, im, im_img, nimg,
                        d->channels, d->height, d->width, d->kernel_h, d->kernel_w, d->pad_h,
                        d->pad_w, d->stride_h, d->stride_w, d->dilation_h, d->dilation_w, d->out_h,
@@ -2280,6 +2329,7 @@ int im2col_core(const float* im, int64_t im_img, int nimg, const rram_conv_desc*
     return launch_status("im2col");
   }
   const int gx = static_cast<int>(std::min<int64_t>((P + 255) / 256, 64));
+  if (plan_note("im2col")) return RRAM_OK;
   hipLaunchKernelGGL(k_im2col, dim3(gx, rows), dim3(256), 0, s, im, im_img, nimg,
                      d->channels, d->height, d->width, d->kernel_h, d->kernel_w, d->pad_h,
                      d->pad_w, d->stride_h, d->stride_w, d->dilation_h, d->dilation_w, d->out_h,
@@ -2291,6 +2341,7 @@ int col2im_core(const float* col, int64_t ldcol, int nimg, const rram_conv_desc*
                 int64_t im_img, int accumulate, hipStream_t s) {
   const int64_t total = (int64_t)nimg * d->channels * d->height * d->width;
   if (total == 0) return RRAM_OK;
+  if (plan_note("col2im")) return RRAM_OK;
   hipLaunchKernelGGL(k_col2im, dim3(stream_blocks(total)), dim3(256), 0, s, col, ldcol, nimg,
                      d->channels, d->height, d->width, d->kernel_h, d->kernel_w, d->pad_h,
                      d->pad_w, d->stride_h, d->stride_w, d->dilation_h, d->dilation_w, d->out_h,
@@ -2305,8 +2356,36 @@ int gemv_core(int trans, int M, int N, float alpha, const float* A, const float*
   if (outs == 0) return RRAM_OK;
   RRAM_REQUIRE(A && x && y, "gemv: NULL");
   const int blocks = (outs + 3) / 4 < 2048 ? (outs + 3) / 4 : 2048;
+  if (plan_note("gemv")) return RRAM_OK;
   hipLaunchKernelGGL(k_gemv, dim3(blocks), dim3(256), 0, s, trans, M, N, alpha, A, x, beta, y);
   return launch_status("gemv");
+}
+
+// Every instantiated kernel of this file, one id per line (rram_f32_kernel_list):
+// k_gemm per dispatch() combination and launch<>() tile, then the rest.
+std::string f32_kernel_list() {
+  std::string out;
+#define RRAM_X(A_, B_, O_) \
+  for (const auto& t : kTiles16) out += gemm_id(A_, B_, O_, 16, t[0], t[1], 0) + "\n";
+  RRAM_GEMM_LIST16(RRAM_X)
+#undef RRAM_X
+#define RRAM_X(A_, B_, O_) \
+  for (const auto& t : kTiles32) out += gemm_id(A_, B_, O_, 32, t[0], t[1], 0) + "\n";
+  RRAM_GEMM_LIST32(RRAM_X)
+#undef RRAM_X
+  out += "gemm2<KCV,KCV,ROWMAJOR,3>\n";
+  char b[64];
+#define RRAM_X(KH_, CPH_, MI_, PD_)                                          \
+  snprintf(b, sizeof b, "patch_f32<%d,%d,%d,%d>\n", KH_, CPH_, MI_, PD_);   \
+  out += b;
+  RRAM_PATCH_F32_LIST(RRAM_X)
+#undef RRAM_X
+  for (const char* k : {"patch_pack", "gemv", "gemv_groups", "im2col", "im2col4", "col2im", "reduce", "reduce_groups",
+                        "reduce_nchw", "reduce_dwdb", "reduce_wave"}) {
+    out += k;
+    out += "\n";
+  }
+  return out;
 }
 
 }  // namespace rram

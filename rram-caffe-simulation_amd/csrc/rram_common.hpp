@@ -39,6 +39,32 @@ void clear_error();
 // Check the launch just issued (hipGetLastError) and return its status.
 int launch_status(const char* what);
 
+// Kernel-id queries (rram_gemm_kernel_ids and its siblings, host only): while
+// a PlanScope is open on the calling thread the fp32 engine's entry points
+// run their own planning code, but every launch site appends its kernel's id
+// to the scope's text (one line per launch, in launch order) instead of
+// launching, and nothing is allocated or copied.  The operand pointers of such
+// a call are never dereferenced: only their alignment is read.
+//   if (plan_note("reduce")) return RRAM_OK;   // at a launch site
+bool planning();
+bool plan_note(const char* fmt, ...);
+struct PlanScope {
+  std::string text;
+  PlanScope();
+  ~PlanScope();
+  PlanScope(const PlanScope&) = delete;
+  PlanScope& operator=(const PlanScope&) = delete;
+};
+// snprintf's contract: the text's length, at most cap - 1 characters of it written
+inline int copy_text(const std::string& t, char* out, size_t cap) {
+  if (out != nullptr && cap > 0) {
+    const size_t n = t.size() < cap - 1 ? t.size() : cap - 1;
+    t.copy(out, n);
+    out[n] = 0;
+  }
+  return static_cast<int>(t.size());
+}
+
 inline hipStream_t as_stream(rram_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Streaming-kernel geometry: 256 threads, at most 8 blocks per CU x 256 CUs,
@@ -155,4 +181,6 @@ struct WPack {
 };
 int conv_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, const float* w, const float* bias,
                 float* y, void* y_oct, int relu, hipStream_t s, const WPack& wk = WPack{});
+// the id of the bf16x6 kernel conv_x6_fwd launches for d, or "f32" (rram_conv_fwd_kernel_id)
+std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16);
 }  // namespace rram

@@ -3278,6 +3278,10 @@ int conv_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, cons
   if (wk.query == nullptr && (reinterpret_cast<uintptr_t>(w) & 3u) != 0) return 0;
   // the epilogues' 32-bit output offsets also hold a strided (Concat-slice) image stride
   if (wk.y_img > 0 && (int64_t)d->num * wk.y_img * 4 >= (1ll << 31)) return 0;
+  if (planning()) {  // a kernel-id query: one line naming the kernel the calls below would launch
+    const std::string id = conv_fwd_kernel_id(d, (reinterpret_cast<uintptr_t>(x) & 15u) == 0);
+    return id != "f32" && plan_note("x6:%s", id.c_str()) ? 1 : 0;
+  }
   {
     const int rc = conv_cb_x6_fwd(d, x, x_oct, w, bias, y, y_oct, relu, s, wk);
     if (rc != 0) return rc;
@@ -3514,6 +3518,7 @@ int gemm_x6_nt(int M, int N, int K, float alpha, const float* A, int lda, const 
   if ((int64_t)(N - 1) * ldb * 4 + (int64_t)K * 4 >= (1ll << 32)) return 0;  // 32-bit buffer offsets
   GemmPlan pl;
   if (!gemm_x6_plan(M, N, K, ws != nullptr ? ws_bytes : 0, pl)) return 0;
+  if (plan_note("x6:gemm<%d,%d>/s%d", pl.MI, pl.NJ, pl.split)) return 1;  // the other engine: one line
   const int MI = pl.MI, BMc = 32 * MI, tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, ktiles = pl.ktiles;
   const int split = pl.split, ktc = pl.ktc;
   const int64_t tiles = (int64_t)tiles_m * tiles_n;
@@ -3622,17 +3627,7 @@ int rram_conv_octet_plan(const rram_conv_desc* d, int* plan) {
   return 1;
 }
 
-namespace {
-// snprintf's contract: the text's length, at most cap - 1 characters of it written
-int copy_text(const std::string& t, char* out, size_t cap) {
-  if (out != nullptr && cap > 0) {
-    const size_t n = std::min(t.size(), cap - 1);
-    memcpy(out, t.data(), n);
-    out[n] = 0;
-  }
-  return static_cast<int>(t.size());
-}
-}  // namespace
+using rram::copy_text;
 
 int rram_conv_fwd_kernel_id(const rram_conv_desc* d_in, int x_align16, char* out, size_t cap) {
   RRAM_REQUIRE(d_in != nullptr, "kernel id query: desc is NULL");

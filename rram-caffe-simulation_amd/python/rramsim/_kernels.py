@@ -138,6 +138,13 @@ SIGNATURES = {
     "rram_conv_octet_plan": (I, [P, P]),
     "rram_conv_fwd_kernel_id": (I, [P, I, C.c_char_p, SZ]),
     "rram_conv_fwd_kernel_list": (I, [C.c_char_p, SZ]),
+    "rram_gemm_kernel_ids": (I, [I, I, I, I, I, I, I, I, I, I, SZ, C.c_char_p, SZ]),
+    "rram_ip_fwd_kernel_ids": (I, [I, I, I, I, I, I, I, I, SZ, C.c_char_p, SZ]),
+    "rram_ip_bwd_kernel_ids": (I, [I, I, I, I, I, I, I, I, C.c_char_p, SZ]),
+    "rram_ip_fwd_groups_kernel_ids": (I, [I, I, I, I, I, I64, I, SZ, C.c_char_p, SZ]),
+    "rram_conv_fwd_kernel_ids": (I, [P, I, I, C.c_char_p, SZ]),
+    "rram_conv_bwd_kernel_ids": (I, [P, I, I, I, SZ, I, I, C.c_char_p, SZ]),
+    "rram_f32_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_conv_weight_pack_bytes": (SZ, [P]),
     "rram_conv2d_fwd_cached": (I, [P, P, P, P, P, I, P, P, P, I, P]),
     "rram_conv2d_fwd_strided": (I, [P, P, P, P, P, I, P, P, C.c_int64, I, P]),

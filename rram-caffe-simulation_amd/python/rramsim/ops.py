@@ -323,6 +323,65 @@ def conv_fwd_kernel_list():
     return buf.value.decode().split()
 
 
+def _id_lines(fn, *args):
+    """A kernel-id query of the fp32 engine (snprintf style) as a list of lines."""
+    buf = C.create_string_buffer(4096)
+    n = fn(*args, buf, len(buf))
+    if n < 0:
+        K.check(n, "kernel ids")
+    return buf.value.decode().split("\n")[:-1] if n else []
+
+
+def gemm_kernel_ids(trans_a, trans_b, M, N, K_, lda=None, ldb=None, a_align16=True, b_align16=True, beta_zero=True,
+                    ws_bytes=0):
+    """One id per kernel gemm_ex would launch now (rram_gemm_kernel_ids; host only)."""
+    lda = (M if trans_a else K_) if lda is None else lda
+    ldb = (K_ if trans_b else N) if ldb is None else ldb
+    return _id_lines(_lib().rram_gemm_kernel_ids, int(trans_a), int(trans_b), M, N, K_, lda, ldb, int(a_align16),
+                     int(b_align16), int(beta_zero), int(ws_bytes))
+
+
+def ip_fwd_kernel_ids(M, N, K_, transpose=False, x_align16=True, w_align16=True, bias=True, relu=False, ws_bytes=0):
+    return _id_lines(_lib().rram_ip_fwd_kernel_ids, M, N, K_, int(transpose), int(x_align16), int(w_align16),
+                     int(bias), int(relu), int(ws_bytes))
+
+
+def ip_bwd_kernel_ids(M, N, K_, transpose=False, dw=True, db=True, dx=True, align16=True):
+    return _id_lines(_lib().rram_ip_bwd_kernel_ids, M, N, K_, int(transpose), int(dw), int(db), int(dx),
+                     int(align16))
+
+
+def ip_fwd_groups_kernel_ids(G, M, N, K_, transpose=False, w_stride=None, align16=True, ws_bytes=0):
+    w_stride = N * K_ if w_stride is None else w_stride
+    return _id_lines(_lib().rram_ip_fwd_groups_kernel_ids, G, M, N, K_, int(transpose), int(w_stride), int(align16),
+                     int(ws_bytes))
+
+
+def conv_fwd_kernel_ids(d, x_align16=True, w_align16=True):
+    """One id per kernel conv2d_fwd would launch now: the fp32 engine's, or one 'x6:' line."""
+    return _id_lines(_lib().rram_conv_fwd_kernel_ids, C.byref(d), int(x_align16), int(w_align16))
+
+
+def conv_bwd_kernel_ids(d, dw=True, db=True, dx=True, ws_bytes=0, w_flipped=False, w_align16=True):
+    return _id_lines(_lib().rram_conv_bwd_kernel_ids, C.byref(d), int(dw), int(db), int(dx), int(ws_bytes),
+                     int(w_flipped), int(w_align16))
+
+
+def f32_kernel_list():
+    """Ids of every instantiated kernel of the fp32 engine (no /sS split suffix)."""
+    n = _lib().rram_f32_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_f32_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
+def conv2d_bwd_ex(d, x, w, w_flipped, dy, dw=None, db=None, dx=None, workspace=None):
+    """rram_conv2d_bwd_ex: conv2d_bwd with the caller's flipped copy of w (or None)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_conv2d_bwd_ex(C.byref(d), _p(x), _p(w), _p(w_flipped), _p(dy), _p(dw), _p(db), _p(dx),
+                                      _p(workspace), wsb, _stream()), "conv2d_bwd_ex")
+
+
 def pack_octets(x, oct_, n, c, h, w):
     K.check(_lib().rram_pack_octets(_p(x), _p(oct_), n, c, h, w, _stream()), "pack_octets")
 
