@@ -789,6 +789,52 @@ int rram_euclidean_loss_bwd(const float* diff, float* dx, int64_t n, float alpha
 int rram_concat_copy(const float* src, float* dst, int num, int src_channels_x_inner,
                      int dst_channels_x_inner, int offset_x_inner, int backward,
                      rram_stream_t s);
+/* Which kernels of the support layers above an entry point would launch right
+ * now (host only, as rram_gemm_kernel_ids: the entry point's own dispatch runs
+ * with its launches recorded instead of issued, nothing is allocated, copied
+ * or dereferenced; snprintf-style result, one line per launch in launch order):
+ *   relu_fwd relu_bwd concat i32_to_f32 euclidean_fwd scale_copy
+ *   pool_planes<K> ppb=N      staged planes, K = 0 | 2 | 3, N planes per block
+ *   pool_planes_sep3 ppb=N    the separable 3x3 / 1 MAX pool without a mask
+ *   pool_max_fixed<K> pool_fwd pool_bwd_plane pool_bwd
+ *   lrn_fwd_slide<SIZE> lrn_fwd lrn_bwd lrn_within_fwd lrn_within_bwd_plane lrn_within_bwd
+ *   softmax_reg<16> softmax
+ *   softmax_loss_fwd softmax_loss_fwd_groups fold_groups softmax_loss_fwd_bwd count_valid softmax_loss_bwd
+ *   accuracy_small accuracy_fused accuracy accuracy_ratio accuracy_small_groups
+ * with_mask / with_ratio / fold: that nullable output (mask, ratio, acc_sum
+ * with acc_row[s]) is given; relu: the entry's _relu_ form.
+ *   rram_pool_fwd_kernel_ids         rram_pool_fwd / rram_pool_relu_fwd
+ *   rram_pool_bwd_kernel_ids         rram_pool_bwd / rram_pool_relu_bwd
+ *   rram_lrn_fwd_kernel_ids          rram_lrn_fwd
+ *   rram_lrn_within_bwd_kernel_ids   rram_lrn_within_bwd / rram_lrn_within_relu_bwd
+ *   rram_softmax_kernel_ids          rram_softmax_fwd
+ *   rram_softmax_loss_kernel_ids     form RRAM_LOSS_*: rram_softmax_loss_fwd_acc, _fwd_groups (G, live), _fwd_bwd, _bwd
+ *   rram_accuracy_kernel_ids         rram_accuracy
+ *   rram_accuracy_groups_kernel_ids  rram_accuracy_groups
+ *   rram_layer_entry_kernel_ids      entry RRAM_ENTRY_*: the entries with a single launch form, on n elements
+ *   rram_layer_kernel_list           every id the above can return, one per line, without " ppb=N" */
+enum { RRAM_LOSS_FWD = 0, RRAM_LOSS_FWD_GROUPS = 1, RRAM_LOSS_FWD_BWD = 2, RRAM_LOSS_BWD = 3 };
+enum {
+  RRAM_ENTRY_RELU_FWD = 0, RRAM_ENTRY_RELU_BWD = 1, RRAM_ENTRY_LRN_BWD = 2, RRAM_ENTRY_LRN_WITHIN_FWD = 3,
+  RRAM_ENTRY_CONCAT = 4, RRAM_ENTRY_EUCLIDEAN_FWD = 5, RRAM_ENTRY_EUCLIDEAN_BWD = 6, RRAM_ENTRY_I32_TO_F32 = 7
+};
+int rram_pool_fwd_kernel_ids(int num, int channels, int height, int width, int pooled_h, int pooled_w, int kernel_h,
+                             int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int method,
+                             int with_mask, int relu, char* out, size_t cap);
+int rram_pool_bwd_kernel_ids(int num, int channels, int height, int width, int pooled_h, int pooled_w, int kernel_h,
+                             int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int method, int relu,
+                             char* out, size_t cap);
+int rram_lrn_fwd_kernel_ids(int num, int channels, int height, int width, int size, char* out, size_t cap);
+int rram_lrn_within_bwd_kernel_ids(int num, int channels, int height, int width, int size, int relu, char* out,
+                                   size_t cap);
+int rram_softmax_kernel_ids(int outer, int channels, int inner, char* out, size_t cap);
+int rram_softmax_loss_kernel_ids(int form, int G, int outer, int channels, int inner, int ignore_label, int fold,
+                                 int live, char* out, size_t cap);
+int rram_accuracy_kernel_ids(int outer, int channels, int inner, int with_ratio, char* out, size_t cap);
+int rram_accuracy_groups_kernel_ids(int G, int outer, int channels, int inner, int fold, int live, char* out,
+                                    size_t cap);
+int rram_layer_entry_kernel_ids(int entry, int64_t n, char* out, size_t cap);
+int rram_layer_kernel_list(char* out, size_t cap);
 /* Dropout train mode: mask from Philox(seed, layer, index); y = x*scale or 0. */
 int rram_dropout_fwd(const float* x, float* y, unsigned int* mask, int64_t n,
                      float ratio, uint64_t seed, uint32_t layer_id, uint64_t iter,

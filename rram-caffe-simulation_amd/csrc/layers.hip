@@ -1064,7 +1064,8 @@ int rram_relu_fwd(const float* x, float* y, int64_t n, float slope, rram_stream_
   RRAM_REQUIRE_I32(n, "relu");
   if (n == 0) return RRAM_OK;
   RRAM_REQUIRE(x && y, "relu: NULL");
-  hipLaunchKernelGGL(k_relu_fwd, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), x, y, n, slope);
+  if (!plan_note("relu_fwd"))
+    hipLaunchKernelGGL(k_relu_fwd, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), x, y, n, slope);
   return launch_status("relu_fwd");
 }
 int rram_relu_bwd(const float* x, const float* dy, float* dx, int64_t n, float slope, rram_stream_t s) {
@@ -1072,7 +1073,8 @@ int rram_relu_bwd(const float* x, const float* dy, float* dx, int64_t n, float s
   RRAM_REQUIRE_I32(n, "relu");
   if (n == 0) return RRAM_OK;
   RRAM_REQUIRE(x && dy && dx, "relu: NULL");
-  hipLaunchKernelGGL(k_relu_bwd, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), x, dy, dx, n, slope);
+  if (!plan_note("relu_bwd"))
+    hipLaunchKernelGGL(k_relu_bwd, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), x, dy, dx, n, slope);
   return launch_status("relu_bwd");
 }
 
@@ -1104,23 +1106,28 @@ int pool_fwd_core(const float* x, float* y, int* mask, int num, int C, int H, in
       // pools 554 -> 391 us per map; its stride-2 form (two new row maxima
       // per output) ran slower than k_pool_planes on pool1 / pool3 / pool4
       const int nseg = (PH + kSepRows - 1) / kSepRows;
+      if (plan_note("pool_planes_sep3 ppb=%d", ppb)) return RRAM_OK;
       hipLaunchKernelGGL(k_pool_planes_sep3, grid, dim3(kThreads), lds, s, x, y, planes, H, W, PH, PW, ph, pw, ppb,
                          nseg, 1.0f / static_cast<float>(PW), 1.0f / static_cast<float>(nseg), relu, slope);
       return launch_status("pool_fwd");
     }
     const int k = method == RRAM_POOL_MAX && kh == kw && (kh == 3 || kh == 2) ? kh : 0;
     auto kern = k == 3 ? k_pool_planes<3> : k == 2 ? k_pool_planes<2> : k_pool_planes<0>;
+    if (plan_note("pool_planes<%d> ppb=%d", k, ppb)) return RRAM_OK;
     hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, s, x, y, mask, planes, H, W, PH, PW, kh, kw, sh, sw, ph, pw,
                        method, ppb, inv_phw, inv_pw, relu, slope);
-  } else if (method == RRAM_POOL_MAX && kh == kw && kh == 3)
-    hipLaunchKernelGGL(k_pool_max_fixed<3>, dim3(stream_blocks(total)), dim3(kThreads), 0, s, x, y, mask, num, C, H,
-                       W, PH, PW, sh, sw, ph, pw, relu, slope);
-  else if (method == RRAM_POOL_MAX && kh == kw && kh == 2)
-    hipLaunchKernelGGL(k_pool_max_fixed<2>, dim3(stream_blocks(total)), dim3(kThreads), 0, s, x, y, mask, num, C, H,
-                       W, PH, PW, sh, sw, ph, pw, relu, slope);
-  else
+  } else if (method == RRAM_POOL_MAX && kh == kw && kh == 3) {
+    if (!plan_note("pool_max_fixed<3>"))
+      hipLaunchKernelGGL(k_pool_max_fixed<3>, dim3(stream_blocks(total)), dim3(kThreads), 0, s, x, y, mask, num, C, H,
+                         W, PH, PW, sh, sw, ph, pw, relu, slope);
+  } else if (method == RRAM_POOL_MAX && kh == kw && kh == 2) {
+    if (!plan_note("pool_max_fixed<2>"))
+      hipLaunchKernelGGL(k_pool_max_fixed<2>, dim3(stream_blocks(total)), dim3(kThreads), 0, s, x, y, mask, num, C, H,
+                         W, PH, PW, sh, sw, ph, pw, relu, slope);
+  } else if (!plan_note("pool_fwd")) {
     hipLaunchKernelGGL(k_pool_fwd, dim3(stream_blocks(total)), dim3(kThreads), 0, s, x, y, mask, num, C, H, W, PH,
                        PW, kh, kw, sh, sw, ph, pw, method, relu, slope);
+  }
   return launch_status("pool_fwd");
 }
 }  // namespace
@@ -1154,10 +1161,12 @@ int rram_pool_relu_bwd(const float* dy, const int* mask, float* dx, int num, int
   // plane path: one 256-thread block per (n, c) plane; the grid's work-item
   // count (num * C * 256) must stay a 32-bit value, else the grid-stride form
   if (method == RRAM_POOL_MAX && H * W <= kBwdPlaneMax && PH * PW <= 1024 && (int64_t)num * C <= (1ll << 24)) {
+    if (plan_note("pool_bwd_plane")) return RRAM_OK;
     hipLaunchKernelGGL(k_pool_bwd_plane, dim3(static_cast<unsigned>(num * C)), dim3(256), 0, as_stream(s), dy, mask,
                        dx, H, W, PH, PW, make_fastdivi(W), kh, kw, sh, sw, ph, pw, relu_y, relu_slope);
     return launch_status("pool_bwd");
   }
+  if (plan_note("pool_bwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_pool_bwd, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), dy,
                      mask, dx, num, C, H, W, PH, PW, kh, kw, sh, sw, ph, pw, method, relu_y, relu_slope);
   return launch_status("pool_bwd");
@@ -1172,15 +1181,18 @@ int rram_lrn_fwd(const float* x, float* y, float* scale, int num, int C, int H, 
   if (total == 0) return RRAM_OK;
   RRAM_REQUIRE(x && y, "lrn_fwd: NULL");
   const int cols = num * H * W;
-  if (size == 5)
-    hipLaunchKernelGGL(k_lrn_fwd_slide<5>, dim3((cols + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(s), x, y,
-                       scale, num, C, H * W, alpha / size, beta, k);
-  else if (size == 3)
-    hipLaunchKernelGGL(k_lrn_fwd_slide<3>, dim3((cols + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(s), x, y,
-                       scale, num, C, H * W, alpha / size, beta, k);
-  else
+  if (size == 5) {
+    if (!plan_note("lrn_fwd_slide<5>"))
+      hipLaunchKernelGGL(k_lrn_fwd_slide<5>, dim3((cols + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(s), x,
+                         y, scale, num, C, H * W, alpha / size, beta, k);
+  } else if (size == 3) {
+    if (!plan_note("lrn_fwd_slide<3>"))
+      hipLaunchKernelGGL(k_lrn_fwd_slide<3>, dim3((cols + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(s), x,
+                         y, scale, num, C, H * W, alpha / size, beta, k);
+  } else if (!plan_note("lrn_fwd")) {
     hipLaunchKernelGGL(k_lrn_fwd, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), x, y,
                        scale, num, C, H * W, size, alpha / size, beta, k);
+  }
   return launch_status("lrn_fwd");
 }
 int rram_lrn_bwd(const float* x, const float* y, const float* scale, const float* dy, float* dx,
@@ -1191,6 +1203,7 @@ int rram_lrn_bwd(const float* x, const float* y, const float* scale, const float
   RRAM_REQUIRE_I32(total, "layer kernel");
   if (total == 0) return RRAM_OK;
   RRAM_REQUIRE(x && y && scale && dy && dx, "lrn_bwd: NULL");
+  if (plan_note("lrn_bwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_lrn_bwd, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), x, y,
                      scale, dy, dx, num, C, H * W, size, 2.0f * alpha * beta / size, beta);
   return launch_status("lrn_bwd");
@@ -1203,6 +1216,7 @@ int rram_lrn_within_fwd(const float* x, float* y, float* scale, int num, int C, 
   RRAM_REQUIRE_I32(total, "layer kernel");
   if (total == 0) return RRAM_OK;
   RRAM_REQUIRE(x && y, "lrn_within_fwd: NULL");
+  if (plan_note("lrn_within_fwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_lrn_within_fwd, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), x, y,
                      scale, (int64_t)num * C, H, W, size, alpha, beta);
   return launch_status("lrn_within_fwd");
@@ -1227,10 +1241,12 @@ int rram_lrn_within_relu_bwd_core(const float* x, const float* scale, const floa
   if (total == 0) return RRAM_OK;
   RRAM_REQUIRE(x && scale && dy && dx, "lrn_within_bwd: NULL");
   if (H * W <= kBwdPlaneMax && (int64_t)num * C <= (1ll << 24)) {  // num * C * 256 work-items fit 32 bits
+    if (plan_note("lrn_within_bwd_plane")) return RRAM_OK;
     hipLaunchKernelGGL(k_lrn_within_bwd_plane, dim3(static_cast<unsigned>(num * C)), dim3(256), 0, as_stream(s), x,
                        scale, dy, dx, H, W, make_fastdivi(W), size, alpha, beta, relu, slope);
     return launch_status("lrn_within_bwd");
   }
+  if (plan_note("lrn_within_bwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_lrn_within_bwd, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), x, scale,
                      dy, dx, (int64_t)num * C, H, W, size, alpha, beta, relu, slope);
   return launch_status("lrn_within_bwd");
@@ -1246,10 +1262,12 @@ int rram_softmax_fwd(const float* x, float* y, int outer, int C, int inner, rram
   RRAM_REQUIRE(x && y, "softmax: NULL");
   int blocks = static_cast<int>((cols + 3) / 4);
   if (blocks > 2048) blocks = 2048;
-  if (C <= 64 * 16)
-    hipLaunchKernelGGL(k_softmax_reg<16>, dim3(blocks), dim3(256), 0, as_stream(s), x, y, outer, C, inner);
-  else
+  if (C <= 64 * 16) {
+    if (!plan_note("softmax_reg<16>"))
+      hipLaunchKernelGGL(k_softmax_reg<16>, dim3(blocks), dim3(256), 0, as_stream(s), x, y, outer, C, inner);
+  } else if (!plan_note("softmax")) {
     hipLaunchKernelGGL(k_softmax, dim3(blocks), dim3(256), 0, as_stream(s), x, y, outer, C, inner);
+  }
   return launch_status("softmax");
 }
 
@@ -1262,6 +1280,7 @@ int rram_softmax_loss_fwd_acc(const float* prob, const float* label, float* out,
   RRAM_REQUIRE(outer >= 0 && C > 0 && inner > 0 && out, "softmax_loss_fwd: bad args");
   RRAM_REQUIRE(outer == 0 || (prob && label), "softmax_loss_fwd: NULL");
   RRAM_REQUIRE(acc_row == nullptr || acc_sum != nullptr, "softmax_loss_fwd: acc_row without acc_sum");
+  if (plan_note("softmax_loss_fwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_softmax_loss_fwd, dim3(1), dim3(1024), 0, as_stream(s), prob, label, out,
                      outer, C, inner, ignore, acc_sum, acc_row);
   return launch_status("softmax_loss_fwd");
@@ -1275,9 +1294,10 @@ int rram_softmax_loss_fwd_groups(const float* prob, const float* label, float* o
   RRAM_REQUIRE(live >= 0 && live <= G, "softmax_loss_fwd_groups: live outside [0, G]");
   RRAM_REQUIRE(acc_rows == nullptr || acc_sum != nullptr, "softmax_loss_fwd_groups: acc_rows without acc_sum");
   if (G == 0) return RRAM_OK;
-  hipLaunchKernelGGL(k_softmax_loss_fwd_groups, dim3(G), dim3(1024), 0, as_stream(s), prob, label, out, outer, C,
-                     inner, ignore);
-  if (acc_sum != nullptr && live > 0)
+  if (!plan_note("softmax_loss_fwd_groups"))
+    hipLaunchKernelGGL(k_softmax_loss_fwd_groups, dim3(G), dim3(1024), 0, as_stream(s), prob, label, out, outer, C,
+                       inner, ignore);
+  if (acc_sum != nullptr && live > 0 && !plan_note("fold_groups"))
     hipLaunchKernelGGL(k_fold_groups, dim3(1), dim3(64), 0, as_stream(s), out, live, acc_sum, acc_rows, row_stride);
   return launch_status("softmax_loss_fwd_groups");
 }
@@ -1289,6 +1309,7 @@ int rram_softmax_loss_fwd_bwd(const float* prob, const float* label, float* out,
   RRAM_REQUIRE(total <= kLossFusedMax, "softmax_loss_fwd_bwd: more than %d elements", kLossFusedMax);
   RRAM_REQUIRE(outer == 0 || (prob && label && dx), "softmax_loss_fwd_bwd: NULL");
   const float scale_all = loss_weight / static_cast<float>((int64_t)outer * inner);
+  if (plan_note("softmax_loss_fwd_bwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_softmax_loss_fwd_bwd, dim3(1), dim3(1024), 0, as_stream(s), prob, label, out, dx, outer, C,
                      inner, ignore, loss_weight, scale_all);
   return launch_status("softmax_loss_fwd_bwd");
@@ -1303,7 +1324,7 @@ int rram_softmax_loss_bwd(const float* prob, const float* label, float* dx, int 
   RRAM_REQUIRE(prob && label && dx, "softmax_loss_bwd: NULL");
   // normalizer = #valid labels; computed on host for the common no-ignore case
   float scale = loss_weight / static_cast<float>((int64_t)outer * inner);
-  if (ignore >= 0) {
+  if (ignore >= 0 && !plan_note("count_valid")) {  // (a kernel-id query allocates and copies nothing)
     float* dcount = nullptr;
     RRAM_HIP_RET(hipMallocAsync(reinterpret_cast<void**>(&dcount), sizeof(float), as_stream(s)));
     hipLaunchKernelGGL(k_count_valid, dim3(1), dim3(1024), 0, as_stream(s), label,
@@ -1314,6 +1335,7 @@ int rram_softmax_loss_bwd(const float* prob, const float* label, float* dx, int 
     RRAM_HIP_RET(hipFreeAsync(dcount, as_stream(s)));
     scale = loss_weight / fmaxf(hc, 1.0f);
   }
+  if (plan_note("softmax_loss_bwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_softmax_loss_bwd, dim3(stream_blocks(total)), dim3(kThreads), 0,
                      as_stream(s), prob, label, dx, outer, C, inner, ignore, scale);
   return launch_status("softmax_loss_bwd");
@@ -1333,21 +1355,25 @@ int rram_accuracy_acc(const float* x, const float* label, float* correct, float*
   const int64_t cols = (int64_t)outer * inner;
   RRAM_REQUIRE(cols < (1ll << 24), "accuracy: more than 2^24 samples (float counts would round)");
   if (cols * C <= kAccSmall && C <= 64) {
+    if (plan_note("accuracy_small")) return RRAM_OK;
     hipLaunchKernelGGL(k_accuracy_small, dim3(1), dim3(1024), 0, as_stream(s), x, label, correct, count, ratio,
                        outer, C, inner, top_k, ignore, acc_sum, acc_row);
     return launch_status("accuracy");
   }
   if (cols > 0 && (cols + 3) / 4 <= kAccFusedBlocks) {
+    if (plan_note("accuracy_fused")) return RRAM_OK;
     hipLaunchKernelGGL(k_accuracy_fused, dim3(static_cast<unsigned>((cols + 3) / 4)), dim3(256), 0, as_stream(s), x,
                        label, correct, count, ratio, outer, C, inner, top_k, ignore, acc_sum, acc_row);
     return launch_status("accuracy");
   }
-  RRAM_HIP_RET(hipMemsetAsync(correct, 0, sizeof(float), as_stream(s)));
-  RRAM_HIP_RET(hipMemsetAsync(count, 0, sizeof(float), as_stream(s)));
-  if (cols > 0)
+  if (!planning()) {
+    RRAM_HIP_RET(hipMemsetAsync(correct, 0, sizeof(float), as_stream(s)));
+    RRAM_HIP_RET(hipMemsetAsync(count, 0, sizeof(float), as_stream(s)));
+  }
+  if (cols > 0 && !plan_note("accuracy"))
     hipLaunchKernelGGL(k_accuracy, dim3(static_cast<unsigned>((cols + 3) / 4)), dim3(256), 0, as_stream(s), x,
                        label, correct, count, outer, C, inner, top_k, ignore);
-  if (ratio)
+  if (ratio && !plan_note("accuracy_ratio"))
     hipLaunchKernelGGL(k_accuracy_ratio, dim3(1), dim3(1), 0, as_stream(s), correct, count, ratio, acc_sum, acc_row);
   return launch_status("accuracy");
 }
@@ -1374,9 +1400,10 @@ int rram_accuracy_groups(const float* x, const float* label, float* correct, flo
     }
     return RRAM_OK;
   }
-  hipLaunchKernelGGL(k_accuracy_small_groups, dim3(G), dim3(1024), 0, as_stream(s), x, label, correct, count, ratio,
-                     outer, C, inner, top_k, ignore);
-  if (acc_sum != nullptr && live > 0)
+  if (!plan_note("accuracy_small_groups"))
+    hipLaunchKernelGGL(k_accuracy_small_groups, dim3(G), dim3(1024), 0, as_stream(s), x, label, correct, count, ratio,
+                       outer, C, inner, top_k, ignore);
+  if (acc_sum != nullptr && live > 0 && !plan_note("fold_groups"))
     hipLaunchKernelGGL(k_fold_groups, dim3(1), dim3(64), 0, as_stream(s), ratio, live, acc_sum, acc_rows, row_stride);
   return launch_status("accuracy_groups");
 }
@@ -1386,6 +1413,7 @@ int rram_i32_to_f32(const int* x, float* y, int64_t n, rram_stream_t s) {
   RRAM_REQUIRE_I32(n, "i32_to_f32");
   if (n == 0) return RRAM_OK;
   RRAM_REQUIRE(x && y, "i32_to_f32: NULL");
+  if (plan_note("i32_to_f32")) return RRAM_OK;
   hipLaunchKernelGGL(k_i32_to_f32, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), x, y, n);
   return launch_status("i32_to_f32");
 }
@@ -1394,6 +1422,7 @@ int rram_euclidean_loss_fwd(const float* a, const float* b, float* diff, float* 
                             rram_stream_t s) {
   RRAM_REQUIRE(n >= 0 && num > 0 && loss_out, "euclidean_loss_fwd: bad args");
   RRAM_REQUIRE(n == 0 || (a && b && diff), "euclidean_loss_fwd: NULL");
+  if (plan_note("euclidean_fwd")) return RRAM_OK;
   hipLaunchKernelGGL(k_euclidean_fwd, dim3(1), dim3(1024), 0, as_stream(s), a, b, diff, loss_out, n, num);
   return launch_status("euclidean_loss_fwd");
 }
@@ -1403,6 +1432,7 @@ int rram_euclidean_loss_bwd(const float* diff, float* dx, int64_t n, float alpha
   RRAM_REQUIRE_I32(n, "euclidean_loss_bwd");
   if (n == 0) return RRAM_OK;
   RRAM_REQUIRE(diff && dx, "euclidean_loss_bwd: NULL");
+  if (plan_note("scale_copy")) return RRAM_OK;
   hipLaunchKernelGGL(k_scale_copy, dim3(stream_blocks(n)), dim3(kThreads), 0, as_stream(s), diff, dx, n, alpha);
   return launch_status("euclidean_loss_bwd");
 }
@@ -1415,9 +1445,117 @@ int rram_concat_copy(const float* src, float* dst, int num, int sci, int dci, in
   RRAM_REQUIRE_I32(total, "layer kernel");
   if (total == 0) return RRAM_OK;
   RRAM_REQUIRE(src && dst, "concat: NULL");
+  if (plan_note("concat")) return RRAM_OK;
   hipLaunchKernelGGL(k_concat, dim3(stream_blocks(total)), dim3(kThreads), 0, as_stream(s), src, dst,
                      num, sci, dci, off, backward);
   return launch_status("concat");
+}
+
+// ---- which kernels of this file an entry point would launch (host only) ----
+// As the fp32 engine's queries (conv_api.hip): each opens a PlanScope and calls
+// the entry point itself with operand pointers that are never dereferenced, so
+// the ids and a staged pool's planes per block come from the dispatch above.
+namespace {
+float* layer_ptr() { return reinterpret_cast<float*>(uintptr_t{1} << 20); }
+int layer_result(int rc, const PlanScope& sc, char* out, size_t cap) { return rc ? rc : copy_text(sc.text, out, cap); }
+}  // namespace
+
+int rram_pool_fwd_kernel_ids(int num, int C, int H, int W, int PH, int PW, int kh, int kw, int sh, int sw, int ph,
+                             int pw, int method, int with_mask, int relu, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  int* m = with_mask ? reinterpret_cast<int*>(p) : nullptr;
+  const int rc = relu ? rram_pool_relu_fwd(p, p, m, num, C, H, W, PH, PW, kh, kw, sh, sw, ph, pw, method, 0.0f, nullptr)
+                      : rram_pool_fwd(p, p, m, num, C, H, W, PH, PW, kh, kw, sh, sw, ph, pw, method, nullptr);
+  return layer_result(rc, sc, out, cap);
+}
+int rram_pool_bwd_kernel_ids(int num, int C, int H, int W, int PH, int PW, int kh, int kw, int sh, int sw, int ph,
+                             int pw, int method, int relu, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  const int* m = reinterpret_cast<const int*>(p);
+  const int rc = relu ? rram_pool_relu_bwd(p, m, p, num, C, H, W, PH, PW, kh, kw, sh, sw, ph, pw, method, p, 0.0f, nullptr)
+                      : rram_pool_bwd(p, m, p, num, C, H, W, PH, PW, kh, kw, sh, sw, ph, pw, method, nullptr);
+  return layer_result(rc, sc, out, cap);
+}
+int rram_lrn_fwd_kernel_ids(int num, int C, int H, int W, int size, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  return layer_result(rram_lrn_fwd(p, p, p, num, C, H, W, size, 1e-4f, 0.75f, 1.0f, nullptr), sc, out, cap);
+}
+int rram_lrn_within_bwd_kernel_ids(int num, int C, int H, int W, int size, int relu, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  const int rc = relu ? rram_lrn_within_relu_bwd(p, p, p, p, num, C, H, W, size, 1e-4f, 0.75f, 0.0f, nullptr)
+                      : rram_lrn_within_bwd(p, p, p, p, num, C, H, W, size, 1e-4f, 0.75f, nullptr);
+  return layer_result(rc, sc, out, cap);
+}
+int rram_softmax_kernel_ids(int outer, int C, int inner, char* out, size_t cap) {
+  PlanScope sc;
+  return layer_result(rram_softmax_fwd(layer_ptr(), layer_ptr(), outer, C, inner, nullptr), sc, out, cap);
+}
+int rram_softmax_loss_kernel_ids(int form, int G, int outer, int C, int inner, int ignore, int fold, int live, char* out,
+                                 size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  float* acc = fold ? p : nullptr;
+  int rc = RRAM_EINVAL;
+  switch (form) {
+    case RRAM_LOSS_FWD: rc = rram_softmax_loss_fwd_acc(p, p, p, outer, C, inner, ignore, acc, acc, nullptr); break;
+    case RRAM_LOSS_FWD_GROUPS:
+      rc = rram_softmax_loss_fwd_groups(p, p, p, G, outer, C, inner, ignore, acc, acc, 1, live, nullptr);
+      break;
+    case RRAM_LOSS_FWD_BWD: rc = rram_softmax_loss_fwd_bwd(p, p, p, p, outer, C, inner, ignore, 1.0f, nullptr); break;
+    case RRAM_LOSS_BWD: rc = rram_softmax_loss_bwd(p, p, p, outer, C, inner, ignore, 1.0f, nullptr); break;
+    default: set_error("softmax_loss_kernel_ids: unknown form %d", form);
+  }
+  return layer_result(rc, sc, out, cap);
+}
+int rram_accuracy_kernel_ids(int outer, int C, int inner, int with_ratio, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  return layer_result(rram_accuracy(p, p, p, p, with_ratio ? p : nullptr, outer, C, inner, 1, -1, nullptr), sc, out,
+                      cap);
+}
+int rram_accuracy_groups_kernel_ids(int G, int outer, int C, int inner, int fold, int live, char* out, size_t cap) {
+  PlanScope sc;
+  float* p = layer_ptr();
+  float* acc = fold ? p : nullptr;
+  return layer_result(rram_accuracy_groups(p, p, p, p, p, G, outer, C, inner, 1, -1, acc, acc, 1, live, nullptr), sc,
+                      out, cap);
+}
+int rram_layer_entry_kernel_ids(int entry, int64_t n, char* out, size_t cap) {
+  RRAM_REQUIRE(n >= 0 && n < 2147483647ll, "layer_entry_kernel_ids: n outside [0, 2^31)");
+  PlanScope sc;
+  float* p = layer_ptr();
+  const int ni = static_cast<int>(n);
+  int rc = RRAM_EINVAL;
+  switch (entry) {
+    case RRAM_ENTRY_RELU_FWD: rc = rram_relu_fwd(p, p, n, 0.0f, nullptr); break;
+    case RRAM_ENTRY_RELU_BWD: rc = rram_relu_bwd(p, p, p, n, 0.0f, nullptr); break;
+    case RRAM_ENTRY_LRN_BWD: rc = rram_lrn_bwd(p, p, p, p, p, 1, ni, 1, 1, 5, 1e-4f, 0.75f, nullptr); break;
+    case RRAM_ENTRY_LRN_WITHIN_FWD: rc = rram_lrn_within_fwd(p, p, p, 1, 1, 1, ni, 3, 1e-4f, 0.75f, nullptr); break;
+    case RRAM_ENTRY_CONCAT: rc = rram_concat_copy(p, p, 1, ni, ni, 0, 0, nullptr); break;
+    case RRAM_ENTRY_EUCLIDEAN_FWD: rc = rram_euclidean_loss_fwd(p, p, p, p, n, 1, nullptr); break;
+    case RRAM_ENTRY_EUCLIDEAN_BWD: rc = rram_euclidean_loss_bwd(p, p, n, 1.0f, nullptr); break;
+    case RRAM_ENTRY_I32_TO_F32: rc = rram_i32_to_f32(reinterpret_cast<const int*>(p), p, n, nullptr); break;
+    default: set_error("layer_entry_kernel_ids: unknown entry %d", entry);
+  }
+  return layer_result(rc, sc, out, cap);
+}
+// every id a launch site of this file can record (a staged pool's " ppb=N" left out)
+int rram_layer_kernel_list(char* out, size_t cap) {
+  return copy_text(
+      "relu_fwd\nrelu_bwd\n"
+      "pool_planes<0>\npool_planes<2>\npool_planes<3>\npool_planes_sep3\n"
+      "pool_max_fixed<2>\npool_max_fixed<3>\npool_fwd\npool_bwd_plane\npool_bwd\n"
+      "lrn_fwd_slide<3>\nlrn_fwd_slide<5>\nlrn_fwd\nlrn_bwd\n"
+      "lrn_within_fwd\nlrn_within_bwd_plane\nlrn_within_bwd\n"
+      "softmax_reg<16>\nsoftmax\n"
+      "softmax_loss_fwd\nsoftmax_loss_fwd_groups\nfold_groups\nsoftmax_loss_fwd_bwd\ncount_valid\nsoftmax_loss_bwd\n"
+      "accuracy_small\naccuracy_fused\naccuracy\naccuracy_ratio\naccuracy_small_groups\n"
+      "i32_to_f32\neuclidean_fwd\nscale_copy\nconcat\n",
+      out, cap);
 }
 
 }  // extern "C"

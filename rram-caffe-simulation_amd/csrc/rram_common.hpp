@@ -39,8 +39,9 @@ void clear_error();
 // Check the launch just issued (hipGetLastError) and return its status.
 int launch_status(const char* what);
 
-// Kernel-id queries (rram_gemm_kernel_ids and its siblings, host only): while
-// a PlanScope is open on the calling thread the fp32 engine's entry points
+// Kernel-id queries (rram_gemm_kernel_ids, rram_pool_fwd_kernel_ids and their
+// siblings, host only): while a PlanScope is open on the calling thread the
+// entry points of the fp32 engine and of the support layers (layers.hip)
 // run their own planning code, but every launch site appends its kernel's id
 // to the scope's text (one line per launch, in launch order) instead of
 // launching, and nothing is allocated or copied.  The operand pointers of such

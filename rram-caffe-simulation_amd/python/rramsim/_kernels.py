@@ -24,6 +24,9 @@ RRAM_OK, RRAM_EINVAL, RRAM_EHIP, RRAM_ENOMEM, RRAM_EUNSUPPORTED = 0, -1, -2, -3,
 RRAM_CELL_SINGLE, RRAM_CELL_DIFFPAIR = 0, 1
 RRAM_BIAS_NONE, RRAM_BIAS_ROW, RRAM_BIAS_COL = 0, 1, 2
 RRAM_POOL_MAX, RRAM_POOL_AVE = 0, 1
+RRAM_LOSS_FWD, RRAM_LOSS_FWD_GROUPS, RRAM_LOSS_FWD_BWD, RRAM_LOSS_BWD = range(4)
+LAYER_ENTRIES = {"relu_fwd": 0, "relu_bwd": 1, "lrn_bwd": 2, "lrn_within_fwd": 3, "concat": 4, "euclidean_loss_fwd": 5,
+                 "euclidean_loss_bwd": 6, "i32_to_f32": 7}      # RRAM_ENTRY_*
 RRAM_MAX_SEGS = 32
 TWO32 = 1 << 32
 
@@ -185,6 +188,16 @@ SIGNATURES = {
     "rram_euclidean_loss_fwd": (I, [P, P, P, P, I64, I, P]),
     "rram_euclidean_loss_bwd": (I, [P, P, I64, F, P]),
     "rram_i32_to_f32": (I, [P, P, I64, P]),
+    "rram_pool_fwd_kernel_ids": (I, [I] * 15 + [C.c_char_p, SZ]),
+    "rram_pool_bwd_kernel_ids": (I, [I] * 14 + [C.c_char_p, SZ]),
+    "rram_lrn_fwd_kernel_ids": (I, [I, I, I, I, I, C.c_char_p, SZ]),
+    "rram_lrn_within_bwd_kernel_ids": (I, [I, I, I, I, I, I, C.c_char_p, SZ]),
+    "rram_softmax_kernel_ids": (I, [I, I, I, C.c_char_p, SZ]),
+    "rram_softmax_loss_kernel_ids": (I, [I, I, I, I, I, I, I, I, C.c_char_p, SZ]),
+    "rram_accuracy_kernel_ids": (I, [I, I, I, I, C.c_char_p, SZ]),
+    "rram_accuracy_groups_kernel_ids": (I, [I, I, I, I, I, I, C.c_char_p, SZ]),
+    "rram_layer_entry_kernel_ids": (I, [I, I64, C.c_char_p, SZ]),
+    "rram_layer_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_dropout_fwd": (I, [P, P, P, I64, F, U64, U32, U64, P]),
     "rram_dropout_bwd": (I, [P, P, P, I64, F, P]),
     "rram_bias_add": (I, [P, P, I, I, I, P]),

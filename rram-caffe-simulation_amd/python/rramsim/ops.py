@@ -535,6 +535,72 @@ def accuracy(x, label, correct, count, outer, channels, inner, top_k=1, ignore=-
                                  channels, inner, top_k, ignore, _stream()), "accuracy")
 
 
+def euclidean_loss_fwd(a, b, diff, loss, num):
+    """diff = a - b, loss[0] = sum(diff^2) / num / 2 (rram_euclidean_loss_fwd)."""
+    K.check(_lib().rram_euclidean_loss_fwd(_p(a), _p(b), _p(diff), _p(loss), a.numel(), num, _stream()),
+            "euclidean_loss_fwd")
+
+
+def euclidean_loss_bwd(diff, dx, alpha):
+    K.check(_lib().rram_euclidean_loss_bwd(_p(diff), _p(dx), diff.numel(), alpha, _stream()), "euclidean_loss_bwd")
+
+
+def i32_to_f32(x, y):
+    K.check(_lib().rram_i32_to_f32(_p(x), _p(y), x.numel(), _stream()), "i32_to_f32")
+
+
+# ---- which kernels of the support layers a call would launch (host only; geom as pool_fwd's) ----
+def pool_fwd_kernel_ids(geom, method, mask=True, relu=False):
+    """e.g. ['pool_planes<3> ppb=2'] (rram_pool_fwd_kernel_ids)."""
+    return _id_lines(_lib().rram_pool_fwd_kernel_ids, *geom, method, int(mask), int(relu))
+
+
+def pool_bwd_kernel_ids(geom, method, relu=False):
+    return _id_lines(_lib().rram_pool_bwd_kernel_ids, *geom, method, int(relu))
+
+
+def lrn_fwd_kernel_ids(n, c, h, w, size):
+    return _id_lines(_lib().rram_lrn_fwd_kernel_ids, n, c, h, w, size)
+
+
+def lrn_within_bwd_kernel_ids(n, c, h, w, size, relu=False):
+    return _id_lines(_lib().rram_lrn_within_bwd_kernel_ids, n, c, h, w, size, int(relu))
+
+
+def softmax_kernel_ids(outer, channels, inner):
+    return _id_lines(_lib().rram_softmax_kernel_ids, outer, channels, inner)
+
+
+def softmax_loss_kernel_ids(form, outer, channels, inner, ignore=-1, G=1, fold=False, live=None):
+    """form: 'fwd' | 'fwd_groups' | 'fwd_bwd' | 'bwd' (rram_softmax_loss_kernel_ids)."""
+    form = {"fwd": K.RRAM_LOSS_FWD, "fwd_groups": K.RRAM_LOSS_FWD_GROUPS, "fwd_bwd": K.RRAM_LOSS_FWD_BWD,
+            "bwd": K.RRAM_LOSS_BWD}[form]
+    return _id_lines(_lib().rram_softmax_loss_kernel_ids, form, G, outer, channels, inner, ignore, int(fold),
+                     G if live is None else live)
+
+
+def accuracy_kernel_ids(outer, channels, inner, ratio=True):
+    return _id_lines(_lib().rram_accuracy_kernel_ids, outer, channels, inner, int(ratio))
+
+
+def accuracy_groups_kernel_ids(G, outer, channels, inner, fold=False, live=None):
+    return _id_lines(_lib().rram_accuracy_groups_kernel_ids, G, outer, channels, inner, int(fold),
+                     G if live is None else live)
+
+
+def layer_entry_kernel_ids(entry, n):
+    """entry: a key of K.LAYER_ENTRIES, the entries with a single launch form, on n elements."""
+    return _id_lines(_lib().rram_layer_entry_kernel_ids, K.LAYER_ENTRIES[entry], n)
+
+
+def layer_kernel_list():
+    """Every id the support layers' launch sites can record (no ' ppb=N')."""
+    n = _lib().rram_layer_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_layer_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
 def fill_uniform(x, lo, hi, seed, sid=0):
     K.check(_lib().rram_fill_uniform(_p(x), x.numel(), lo, hi, seed, sid, _stream()), "fill")
 

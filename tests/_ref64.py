@@ -98,6 +98,222 @@ def maxpool64(x, k, s):
     return out
 
 
+# ---------------------------------------------------------------------------
+# Support layers (csrc/layers.hip), vectorised over N and C: the only Python
+# loops run over window taps.  tests/test_gpu_layer_kernel_matrix.py.
+# ---------------------------------------------------------------------------
+FLT_MAX = float(np.finfo(np.float32).max)
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+def pool_shape(H, W, kh, kw, sh, sw, ph, pw):
+    """pooling_layer.cpp:90-104: ceil rule; with padding the last window must start inside the image."""
+    PH = -(-(H + 2 * ph - kh) // sh) + 1
+    PW = -(-(W + 2 * pw - kw) // sw) + 1
+    if ph or pw:
+        if (PH - 1) * sh >= H + ph:
+            PH -= 1
+        if (PW - 1) * sw >= W + pw:
+            PW -= 1
+    return PH, PW
+
+
+def _taps(L, P, k, s, p):
+    """Per tap a < k: (input index clipped into [0, L), inside the image?) for the P window starts."""
+    st = np.arange(P) * s - p
+    return [(np.clip(st + a, 0, L - 1), (st + a >= 0) & (st + a < L)) for a in range(k)]
+
+
+def _ave_size(L, P, k, s, p):
+    """AvePoolForward's divisor along one axis: the window clipped to [-pad, L + pad)."""
+    st = np.arange(P) * s - p
+    return np.minimum(st + k, L + p) - st
+
+
+def maxpool_scan(x, kh, kw, sh, sw, ph, pw):
+    """MaxPoolForward (pooling_layer.cu:11-47) on float32 x [N, C, H, W]: the
+    window clipped to the image, -FLT_MAX start, strict '>' in row-major order,
+    so the first maximum wins and a NaN never does.  (values float32, argmax
+    int32 or -1); comparisons only, so this is exact."""
+    x = np.asarray(x, np.float32)
+    H, W = x.shape[2:]
+    PH, PW = pool_shape(H, W, kh, kw, sh, sw, ph, pw)
+    m = np.full(x.shape[:2] + (PH, PW), -FLT_MAX, np.float32)
+    mi = np.full(m.shape, -1, np.int32)
+    for h, okh in _taps(H, PH, kh, sh, ph):
+        for w, okw in _taps(W, PW, kw, sw, pw):
+            v = x[:, :, h[:, None], w[None, :]]
+            with np.errstate(invalid="ignore"):
+                up = (okh[:, None] & okw[None, :]) & (v > m)
+            m = np.where(up, v, m)
+            mi = np.where(up, (h[:, None] * W + w[None, :]).astype(np.int32), mi)
+    return m, mi
+
+
+def avepool64(x, kh, kw, sh, sw, ph, pw):
+    """AvePoolForward (pooling_layer.cu:52-84): (float64 mean over Caffe's padded window size, Σ|term|)."""
+    x = np.asarray(x, np.float64)
+    H, W = x.shape[2:]
+    PH, PW = pool_shape(H, W, kh, kw, sh, sw, ph, pw)
+    s = np.zeros(x.shape[:2] + (PH, PW))
+    sa = np.zeros_like(s)
+    for h, okh in _taps(H, PH, kh, sh, ph):
+        for w, okw in _taps(W, PW, kw, sw, pw):
+            v = x[:, :, h[:, None], w[None, :]] * (okh[:, None] & okw[None, :])
+            s += v
+            sa += np.abs(v)
+    size = (_ave_size(H, PH, kh, sh, ph)[:, None] * _ave_size(W, PW, kw, sw, pw)[None, :]).astype(np.float64)
+    return s / size, sa / size
+
+
+def maxpool_bwd64(dy, mask, H, W):
+    """MaxPoolBackward: dx[mask] += dy per plane (mask -1: nowhere).  (dx, Σ|term|) float64."""
+    dy = np.asarray(dy, np.float64)
+    N, C = dy.shape[:2]
+    plane = np.arange(N * C, dtype=np.int64).reshape(N, C, 1, 1) * (H * W)
+    ok = mask >= 0
+    idx = (plane + np.where(ok, mask, 0))[ok]
+    dx = np.bincount(idx, weights=dy[ok], minlength=N * C * H * W)
+    sc = np.bincount(idx, weights=np.abs(dy[ok]), minlength=N * C * H * W)
+    return dx.reshape(N, C, H, W), sc.reshape(N, C, H, W)
+
+
+def avepool_bwd64(dy, H, W, kh, kw, sh, sw, ph, pw):
+    """AvePoolBackward (pooling_layer.cu:245-279): every covering window's dy / its padded size."""
+    dy = np.asarray(dy, np.float64)
+    PH, PW = dy.shape[2:]
+    size = (_ave_size(H, PH, kh, sh, ph)[:, None] * _ave_size(W, PW, kw, sw, pw)[None, :]).astype(np.float64)
+    t = dy / size
+    dx = np.zeros(dy.shape[:2] + (H, W))
+    sc = np.zeros_like(dx)
+    for h, okh in _taps(H, PH, kh, sh, ph):
+        for w, okw in _taps(W, PW, kw, sw, pw):     # within one tap every window hits its own element
+            a, b = np.nonzero(okh)[0], np.nonzero(okw)[0]
+            dx[:, :, h[a][:, None], w[b][None, :]] += t[:, :, a[:, None], b[None, :]]
+            sc[:, :, h[a][:, None], w[b][None, :]] += np.abs(t[:, :, a[:, None], b[None, :]])
+    return dx, sc
+
+
+def relu64(v, slope):
+    """relu_layer.cu:9-15 on any float array (slope as the float32 the kernel gets)."""
+    with np.errstate(invalid="ignore"):
+        return np.where(v > 0, v, v * np.asarray(np.float32(slope), v.dtype))
+
+
+def relu_bwd_factor(y, slope):
+    """relu_layer.cu:35-44: (y > 0) + (y <= 0) * slope (a NaN y gives 0)."""
+    with np.errstate(invalid="ignore"):
+        return (y > 0) + (y <= 0) * np.float64(np.float32(slope))
+
+
+def lrn_scale64(x, size, alpha, k=1.0):
+    x = np.asarray(x, np.float64)
+    c = x.shape[1]
+    pre = (size - 1) // 2
+    sq = np.zeros((x.shape[0], c + size - 1) + x.shape[2:])
+    sq[:, pre:pre + c] = x * x
+    s = np.full(x.shape, float(k))
+    for j in range(size):
+        s += (alpha / size) * sq[:, j:j + c]
+    return s
+
+
+def lrn_bwd64(x, y, scale, dy, size, alpha, beta):
+    """LRNComputeDiff (lrn_layer.cu:120-165) of the given x, y, scale, dy:
+    dx = dy scale^-beta - 2 alpha beta / size · x · Σ_{j: c in window j} dy_j y_j / scale_j.  (dx, Σ|term|)."""
+    x, y, scale, dy = (np.asarray(a, np.float64) for a in (x, y, scale, dy))
+    c = x.shape[1]
+    pre = (size - 1) // 2
+    post = size - pre - 1
+    r = np.zeros((x.shape[0], c + size - 1) + x.shape[2:])
+    r[:, post:post + c] = dy * y / scale
+    ra = np.abs(r)
+    acc, acca = np.zeros_like(x), np.zeros_like(x)
+    for j in range(size):                    # channels c - post .. c + pre
+        acc += r[:, j:j + c]
+        acca += ra[:, j:j + c]
+    cr = 2.0 * alpha * beta / size
+    a = dy * np.power(scale, -beta)
+    return a - cr * x * acc, np.abs(a) + cr * np.abs(x) * acca
+
+
+def _within_sizes(H, W, size):
+    pre = (size - 1) // 2
+    return (_ave_size(H, H, size, 1, pre)[:, None] * _ave_size(W, W, size, 1, pre)[None, :]).astype(np.float64)
+
+
+def _window_sum(v, size):
+    """Σ of v over the size x size window centred on each element, clipped to the image."""
+    pre = (size - 1) // 2
+    H, W = v.shape[2:]
+    p = np.zeros(v.shape[:2] + (H + size - 1, W + size - 1))
+    p[:, :, pre:pre + H, pre:pre + W] = v
+    out = np.zeros_like(v)
+    for a in range(size):
+        for b in range(size):
+            out += p[:, :, a:a + H, b:b + W]
+    return out
+
+
+def lrn_within64(x, size, alpha, beta):
+    """lrn_layer.cpp WithinChannelForward: (y, scale) with scale = 1 + alpha · AVE-pool(x²) (Caffe's padded divisor)."""
+    x = np.asarray(x, np.float64)
+    sc = 1.0 + alpha * _window_sum(x * x, size) / _within_sizes(*x.shape[2:], size)
+    return x * np.power(sc, -beta), sc
+
+
+def lrn_within_bwd64(x, scale, dy, size, alpha, beta):
+    """WithinChannelBackward of the given x, scale, dy:
+    dx = dy scale^-beta - 2 alpha beta · x · Σ_{windows p holding the element} dy_p x_p scale_p^(-beta-1) / n_p."""
+    x, scale, dy = (np.asarray(a, np.float64) for a in (x, scale, dy))
+    t = dy * x * np.power(scale, -beta - 1.0) / _within_sizes(*x.shape[2:], size)
+    a = dy * np.power(scale, -beta)
+    return (a - 2.0 * alpha * beta * x * _window_sum(t, size),
+            np.abs(a) + 2.0 * alpha * beta * np.abs(x) * _window_sum(np.abs(t), size))
+
+
+def softmax64(x):
+    """softmax_layer.cu over axis 1 of [outer, C, inner] (-Inf entries allowed beside a finite one)."""
+    x = np.asarray(x, np.float64)
+    e = np.exp(x - x.max(axis=1, keepdims=True))
+    return e / e.sum(axis=1, keepdims=True)
+
+
+def softmax_loss64(prob, label, ignore=-1):
+    """softmax_loss_layer.cpp:95-112: (loss, Σ|term| / N, #valid) with the FLT_MIN clamp."""
+    prob = np.asarray(prob, np.float64)
+    lab = np.asarray(label).astype(np.int64)                    # [outer, inner]
+    valid = np.ones(lab.shape, bool) if ignore < 0 else lab != ignore
+    p = np.take_along_axis(prob, np.where(valid, lab, 0)[:, None, :], 1)[:, 0, :]
+    t = -np.log(np.maximum(p, FLT_MIN)) * valid
+    n = max(int(valid.sum()), 1)
+    return t.sum() / n, np.abs(t).sum() / n, int(valid.sum())
+
+
+def softmax_loss_bwd64(prob, label, ignore=-1, loss_weight=1.0):
+    """softmax_loss_layer.cu backward: (prob - onehot) · loss_weight / #valid, 0 at ignored columns.
+    The scale is the float32 quotient the host (or the fused kernel) forms.  (dx, |prob| + onehot) · scale."""
+    prob = np.asarray(prob, np.float64)
+    lab = np.asarray(label).astype(np.int64)
+    valid = np.ones(lab.shape, bool) if ignore < 0 else lab != ignore
+    onehot = (np.arange(prob.shape[1])[None, :, None] == lab[:, None, :]).astype(np.float64)
+    sc = float(np.float32(loss_weight) / np.float32(max(int(valid.sum()), 1)))
+    v = valid[:, None, :]
+    return (prob - onehot) * sc * v, (np.abs(prob) + onehot) * sc * v
+
+
+def accuracy64(x, label, top_k=1, ignore=-1):
+    """accuracy_layer.cpp:48-90: (#correct, #counted); the label's (value, index) pair within the top_k."""
+    x = np.asarray(x)
+    lab = np.asarray(label).astype(np.int64)
+    valid = np.ones(lab.shape, bool) if ignore < 0 else lab != ignore
+    l0 = np.where(valid, lab, 0)[:, None, :]
+    v = np.take_along_axis(x, l0, 1)
+    c = np.arange(x.shape[1])[None, :, None]
+    rank = ((x > v) | ((x == v) & (c > l0))).sum(axis=1)
+    return int(((rank < top_k) & valid).sum()), int(valid.sum())
+
+
 # fp32-level guard of the bf16x6 engine (tests/test_gpu_fp32_guard.py): per
 # layer, errors in units of Σ|a·b| (max, mean) of the bf16x6 kernel and of the
 # fp32-MFMA kernel on the same data.  The 1e-4 gate above would pass a kernel

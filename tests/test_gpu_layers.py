@@ -83,8 +83,10 @@ def test_pool_fwd_bwd_vs_autograd(device, method, k, s, p):
 @pytest.mark.parametrize("shape,k,s,p", [((8, 64, 28, 28), 3, 1, 1), ((4, 48, 27, 27), 3, 2, 0),
                                          ((3, 7, 64, 64), 2, 2, 0), ((2, 9, 7, 7), 3, 2, 1)])
 def test_max_pool_plane_kernel_equals_direct(device, shape, k, s, p):
-    """The LDS-plane max pool (several planes per block; 64 x 64 planes take
-    the direct kernel) against MaxPoolForward restated (pooling_layer.cu:11-47:
+    """The LDS-plane max pool (one plane per block at these plane counts, the
+    64 x 64 planes included: every shape here is staged, ops.pool_fwd_kernel_ids
+    reports ppb=1; several planes per block and the direct kernels are run by
+    test_gpu_layer_kernel_matrix.py) against MaxPoolForward restated (pooling_layer.cu:11-47:
     window clipped to the image, -FLT_MAX start, strict ">" in row-major
     order): values and argmax mask, bit for bit."""
     import torch
@@ -145,7 +147,8 @@ def _max_pool_scan(xs, k, s, p, PH, PW):
                                        ((2, 9, 9, 10), 1, 0), ((1, 3, 129, 127), 2, 1)])
 def test_max_pool_sep3_equals_scan(device, shape, s, p):
     """The TEST-phase 3 x 3 max pool without argmax (k_pool_planes_sep3: the
-    separable window, several planes per block) against
+    separable window, one plane per block at these plane counts; the stride-2
+    shapes take k_pool_planes<3>, as ops.pool_fwd_kernel_ids reports) against
     MaxPoolForward's scan, bit for bit, with ties of +0 / -0, NaN, +-Inf and
     -FLT_MAX in the input; and the fused-ReLU form against relu() of it."""
     import torch
