@@ -120,6 +120,17 @@ int rram_net_layer_times(rram_net_t net, double* ms, long* counts, int cap, int*
  * writes "name\ttype\tbottoms\ttops\n" lines into out (cap bytes);
  * *needed = bytes required including the terminator. */
 int rram_net_describe(const char* net_prototxt, int phase, char* out, size_t cap, size_t* needed);
+/* Host-only: 1 when the layer registry (layer_factory.hpp) holds `type`. */
+int rram_layer_type_registered(const char* type);
+/* Host-only: what BatchNorm / Scale check of their LayerParameter before they
+ * touch the device.  layer_prototxt: the fields of one `layer { }` message;
+ * num_bottoms, bottom_axes: the bottoms it would be given.  RRAM_EINVAL (with
+ * rram_caffe_last_error) for a BatchNorm `param` spec with a non-zero lr_mult
+ * (batch_norm_layer.cpp:39-48), a bottom of fewer than 2 axes, the two-bottom
+ * Scale, or a Scale axis / num_axes other than 1 / 1.  lr_mult3 (nullable,
+ * BatchNorm): the lr_mult the net records for the three statistics blobs,
+ * 0 where the layer gives no spec. */
+int rram_norm_layer_check(const char* layer_prototxt, int num_bottoms, int bottom_axes, float* lr_mult3);
 
 /* ------------------------------------------------------------- Solver
  * SGDSolver with the fork's fault hooks (solver.cpp:14-40, :237-325).

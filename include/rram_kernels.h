@@ -835,6 +835,77 @@ int rram_accuracy_groups_kernel_ids(int G, int outer, int channels, int inner, i
                                     size_t cap);
 int rram_layer_entry_kernel_ids(int entry, int64_t n, char* out, size_t cap);
 int rram_layer_kernel_list(char* out, size_t cap);
+
+/* ------------------------------------------------------------------------
+ * BatchNorm, Scale and Sigmoid (csrc/norm.hip).  fp32 NC(inner) tensors:
+ * channels = shape(1), inner = count / (num channels); inner == 1 is the
+ * fully-connected case.  Each direction of a BatchNorm (+ Scale + ReLU) is one
+ * per-channel reduction split over slices, a finalize over the slices in a
+ * fixed order (no floating-point atomics: bit-identical from run to run) and
+ * one streaming pass.  Nothing is read back to the host and nothing is
+ * allocated: the caller owns the workspace.
+ * ---------------------------------------------------------------------- */
+/* Floats of workspace the two reductions need for a shape (0: bad shape). */
+size_t rram_norm_workspace_floats(int num, int channels, int64_t inner);
+/* Training statistics (batch_norm_layer.cpp:107-146, replacing its gemv /
+ * powx / axpby chain): mean[c] and the biased variance E((x - E x)^2) over
+ * m = num inner (per-thread shifted sums merged by Chan's formula, never
+ * E[x^2] - E[x]^2), rstd[c] = 1 / sqrt(var + eps), and on the device
+ *   factor = factor maf + 1;  run_mean = mean + maf run_mean;
+ *   run_var = (m > 1 ? m / (m - 1) : 1) var + maf run_var
+ * (run_mean / run_var / factor nullable: no update). */
+int rram_bn_stats_train(const float* x, int num, int channels, int64_t inner, float eps, float maf, float* mean,
+                        float* rstd, float* run_mean, float* run_var, float* factor, float* ws, size_t ws_floats,
+                        rram_stream_t s);
+/* Global statistics (batch_norm_layer.cpp:98-105): s = factor == 0 ? 0 :
+ * 1 / factor; mean = s run_mean; rstd = 1 / sqrt(s run_var + eps). */
+int rram_bn_stats_global(const float* run_mean, const float* run_var, const float* factor, int channels, float eps,
+                         float* mean, float* rstd, rram_stream_t s);
+/* One streaming pass (batch_norm_layer.cpp:148-166, scale_layer.cpp
+ * Forward_cpu, relu_layer.cu:9-15):
+ *   x^ = (x - mean[c]) rstd[c]           (mean == rstd == NULL: x^ = x, the stand-alone Scale)
+ *   y  = gamma ? (beta ? fmaf(x^, gamma[c], beta[c]) : x^ gamma[c]) : x^
+ *   relu: y = y > 0 ? y : y * 0;   xhat_out (nullable) = x^
+ * y may be x.  16-byte accesses when x, y and xhat_out start the same number
+ * of floats (0-3) past a 16-byte boundary, whatever inner is. */
+int rram_norm_apply(const float* x, float* y, float* xhat_out, const float* mean, const float* rstd,
+                    const float* gamma, const float* beta, int relu, int num, int channels, int64_t inner,
+                    rram_stream_t s);
+/* Backward reduction (batch_norm_layer.cpp:187-215, scale_layer.cpp
+ * Backward_cpu): with g = relu_y ? dy [relu_y > 0] : dy, per channel
+ *   dbeta[c] += sum g;  dgamma[c] += sum g xhat     (each nullable)
+ *   coef[3 c ..] = {(gamma ? gamma[c] : 1) (rstd ? rstd[c] : 1), sum g / m, sum g xhat / m}   (nullable)
+ * A stand-alone Scale passes its bottom as xhat. */
+int rram_norm_bwd_reduce(const float* dy, const float* relu_y, const float* xhat, int num, int channels,
+                         int64_t inner, const float* gamma, const float* rstd, float* dgamma, float* dbeta,
+                         float* coef, float* ws, size_t ws_floats, rram_stream_t s);
+/* Backward streaming pass, g as above; dx may be dy.
+ *   coef:  dx = a (g - b - xhat d), {a, b, d} = coef[3 c ..]     (batch_norm_layer.cpp:216-241 with Scale folded)
+ *   NULL:  dx = g (gamma ? gamma[c] : 1) (rstd ? rstd[c] : 1)    (:180-183 global statistics; Scale's dx = dy gamma) */
+int rram_norm_bwd_apply(const float* dy, const float* relu_y, const float* xhat, const float* coef,
+                        const float* gamma, const float* rstd, float* dx, int num, int channels, int64_t inner,
+                        rram_stream_t s);
+/* sigmoid_layer.cu:9-51: y = 1 / (1 + exp(-x)); dx = dy y (1 - y).  y may be x, dx may be dy. */
+int rram_sigmoid_fwd(const float* x, float* y, int64_t n, rram_stream_t s);
+int rram_sigmoid_bwd(const float* y, const float* dy, float* dx, int64_t n, rram_stream_t s);
+/* Which kernels of csrc/norm.hip the entries above launch (host only, as the
+ * queries of the support layers):
+ *   bn_stats_plane<V> bn_stats_cols bn_stats_finalize bn_global_stats norm_apply<V>
+ *   norm_bwd_reduce_plane<V> norm_bwd_reduce_cols norm_bwd_finalize norm_bwd<V> sigmoid_fwd sigmoid_bwd
+ * V = 4 (16-byte accesses) or 1; *_off: the operand's start in floats past a
+ * 16-byte boundary.
+ *   rram_bn_fwd_kernel_ids   statistics (training or global) + rram_norm_apply
+ *   rram_bn_bwd_kernel_ids   rram_norm_bwd_reduce (training statistics, or with_scale) + rram_norm_bwd_apply
+ *   rram_scale_kernel_ids    the stand-alone Scale: forward, or backward = reduce + apply
+ *   rram_norm_kernel_list    every id the above can return, one per line */
+int rram_bn_fwd_kernel_ids(int num, int channels, int64_t inner, int global_stats, int x_off, int y_off, char* out,
+                           size_t cap);
+int rram_bn_bwd_kernel_ids(int num, int channels, int64_t inner, int global_stats, int with_scale, int dy_off,
+                           int dx_off, char* out, size_t cap);
+int rram_scale_kernel_ids(int num, int channels, int64_t inner, int backward, int x_off, int y_off, char* out,
+                          size_t cap);
+int rram_sigmoid_kernel_ids(int64_t n, int backward, char* out, size_t cap);
+int rram_norm_kernel_list(char* out, size_t cap);
 /* Dropout train mode: mask from Philox(seed, layer, index); y = x*scale or 0. */
 int rram_dropout_fwd(const float* x, float* y, unsigned int* mask, int64_t n,
                      float ratio, uint64_t seed, uint32_t layer_id, uint64_t iter,

@@ -397,6 +397,25 @@ int rram_net_layer_times(rram_net_t n, double* ms, long* counts, int cap, int* k
     if (reset) t.clear();
   });
 }
+int rram_layer_type_registered(const char* type) {
+  if (type == nullptr) return 0;
+  const auto& r = LayerRegistry<float>::Registry();
+  return r.find(type) != r.end() ? 1 : 0;
+}
+int rram_norm_layer_check(const char* layer_prototxt, int num_bottoms, int bottom_axes, float* lr_mult3) {
+  return guarded([&] {
+    NEED(layer_prototxt);
+    const Msg lp = parse_prototxt(layer_prototxt);
+    const std::string type = lp.str("type");
+    if (type != "BatchNorm" && type != "Scale") throw Error("norm_layer_check: a BatchNorm or Scale layer is expected");
+    CheckNormLayerParam(lp, num_bottoms, bottom_axes);
+    if (lr_mult3 != nullptr && type == "BatchNorm") {
+      // the layer object itself (its constructor touches no device) through Net's own rule
+      const auto layer = LayerRegistry<float>::CreateLayer(lp);
+      for (int i = 0; i < 3; ++i) lr_mult3[i] = ParamLrMult(*layer, lp, i);
+    }
+  });
+}
 int rram_net_describe(const char* txt, int phase, char* out, size_t cap, size_t* needed) {
   return guarded([&] {
     NEED(txt);

@@ -110,6 +110,21 @@ class Layer {
   // applies the ReLU's backward factor to the bottom diff it writes
   // (rram_pool_relu_bwd); the ReLU's Backward then does nothing
   virtual bool fuse_relu_before_bwd(float /*slope*/) { return false; }
+  // BatchNorm + Scale (+ ReLU) fold (Net::Net, option fuse_bn_scale, any
+  // phase): a BatchNorm whose top's only reader is an in-place channel-wise
+  // Scale (scale_foldable()) applies that layer's gamma / beta in its own
+  // streaming pass and writes their gradients in its backward
+  // (fuse_scale_after; nullptr undoes it); the Scale, folded_into_prev, then
+  // only reshapes and keeps its blobs.  An in-place ReLU of slope 0 right after
+  // such a Scale goes the same way, forward and backward (fuse_relu_after of
+  // the BatchNorm).
+  virtual bool scale_foldable() const { return false; }
+  virtual bool fuse_scale_after(Layer* /*scale*/) { return false; }
+  bool folded_into_prev = false;
+  // a layer whose blobs are never trained whatever the prototxt says
+  // (BatchNorm's statistics, batch_norm_layer.cpp:39-48): the lr_mult Net
+  // records for blob `param` when the layer gives no `param` spec for it
+  virtual bool fixed_lr_mult(int /*param*/, float* /*lr*/) const { return false; }
   // MonteCarlo statistics folded into the producer of a scalar output
   // (Accuracy, SoftmaxWithLoss in TEST): while set, Forward also does
   // *sum += top, *row = top (row nullable) in the kernel that stores the top,
@@ -181,6 +196,13 @@ struct LayerRegisterer {
       #type, [](const ::caffe::Msg& p) -> std::shared_ptr<::caffe::Layer<float>> {  \
         return std::make_shared<type##Layer<float>>(p);                             \
       })
+
+// What BatchNorm and Scale accept of a LayerParameter (host/norm_layers.cpp),
+// as their LayerSetUp checks it and without touching the device
+// (rram_norm_layer_check): throws caffe::Error on a BatchNorm `param` spec
+// with a non-zero lr_mult, a bottom of fewer than 2 axes, the two-bottom
+// Scale, or a Scale axis / num_axes other than the channel-wise 1 / 1.
+void CheckNormLayerParam(const Msg& layer_param, int num_bottoms, int bottom_axes);
 
 // Fill a parameter blob from a FillerParameter message (filler.hpp):
 // constant / gaussian / uniform / xavier / msra, seeded counter RNG.

@@ -143,6 +143,14 @@ int canon_axis_of(const Msg& lp) {
 }
 }  // namespace
 
+float ParamLrMult(const Layer<float>& layer, const Msg& lp, int param_id) {
+  auto specs = lp.subs("param");
+  float lr = 1.0f;
+  if (param_id < (int)specs.size()) lr = static_cast<float>(specs[param_id]->num("lr_mult", 1.0));
+  else layer.fixed_lr_mult(param_id, &lr);
+  return lr;
+}
+
 template <typename Dtype>
 Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(phase) {
   Msg param = InsertSplits(FilterNet(InputsToLayer(in_param), phase));
@@ -157,6 +165,7 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
   const bool fuse_lrn_pool = options.boolean("fuse_lrn_pool", true);
   const bool fuse_concat = options.boolean("fuse_concat", true);
   const bool fuse_conv_y = options.boolean("fuse_conv_y", true);
+  const bool fuse_bn_scale = options.boolean("fuse_bn_scale", true);
   std::vector<int> data_shape;
   {
     std::string ds = options.str("data_shape", "");
@@ -247,7 +256,7 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
     auto pspecs = lp.subs("param");
     for (size_t p = 0; p < layer->blobs().size(); ++p) {
       AppendParam(lid, static_cast<int>(p), lp);
-      const float lr = p < pspecs.size() ? static_cast<float>(pspecs[p]->num("lr_mult", 1.0)) : 1.0f;
+      const float lr = ParamLrMult(*layer, lp, static_cast<int>(p));
       layer->set_param_propagate_down(static_cast<int>(p), lr != 0.0f);
       need_bw = need_bw || lr != 0.0f;
     }
@@ -270,11 +279,29 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
       // a Pooling producer (not itself carrying a folded LRN) stores relu(y)
       if (relu && !relu->folded && prev_makes_it && prev->fuse_relu_after(relu->negative_slope())) relu->folded = true;
     }
+    // BatchNorm -> in-place Scale (-> in-place ReLU, slope 0): the BatchNorm
+    // runs the chain (one streaming launch forward, a reduction and a streaming
+    // launch backward); a second reader of the BatchNorm top would sit behind
+    // a Split layer, so the Scale right after it is its only reader
+    if (fuse_bn_scale && lid > 0 && bottoms.size() == 1 && tops.size() == 1 && bottoms[0] == tops[0]) {
+      const int prev_top = top_id_vecs_[lid - 1].size() == 1 ? top_id_vecs_[lid - 1][0] : -1;
+      if (type == "Scale" && prev_top == bottom_id_vecs_[lid][0] && layers_[lid - 1]->fuse_scale_after(layer.get())) {
+        layer->folded_into_prev = true;
+        // the BatchNorm's backward is now the one that writes dgamma / dbeta:
+        // it runs whenever the Scale's would, also when its own bottom takes no diff
+        layer_need_backward_[lid - 1] = layer_need_backward_[lid - 1] || need_bw;
+      }
+      auto* relu = dynamic_cast<ReLULayer<Dtype>*>(layer.get());
+      if (relu && !relu->folded && lid > 1 && layers_[lid - 1]->folded_into_prev &&
+          prev_top == bottom_id_vecs_[lid][0] && layers_[lid - 2]->fuse_relu_after(relu->negative_slope()))
+        relu->folded = relu->bwd_folded = true;
+    }
     // the backward mirror: a layer whose single bottom is the top of the
     // in-place ReLU right before it applies that ReLU's backward factor
     if (fuse_relu && lid > 0 && bottoms.size() == 1) {
       auto* relu = dynamic_cast<ReLULayer<Dtype>*>(layers_[lid - 1].get());
-      if (relu && bottom_vecs_[lid - 1].size() == 1 && top_id_vecs_[lid - 1].size() == 1 &&
+      // (not when a BatchNorm fold above already took that ReLU's backward)
+      if (relu && !relu->bwd_folded && bottom_vecs_[lid - 1].size() == 1 && top_id_vecs_[lid - 1].size() == 1 &&
           bottom_id_vecs_[lid - 1][0] == top_id_vecs_[lid - 1][0] && top_id_vecs_[lid - 1][0] == bottom_id_vecs_[lid][0] &&
           layer->fuse_relu_before_bwd(relu->negative_slope()))
         relu->bwd_folded = true;
@@ -494,7 +521,7 @@ void Net<Dtype>::AppendParam(int layer_id, int param_id, const Msg& lp) {
   if (!pname.empty()) param_names_index_[pname] = net_param_id;
   const int learnable_id = static_cast<int>(learnable_params_.size());
   learnable_params_.push_back(params_[net_param_id].get());
-  params_lr_.push_back(spec ? static_cast<float>(spec->num("lr_mult", 1.0)) : 1.0f);
+  params_lr_.push_back(ParamLrMult(*layers_[layer_id], lp, param_id));
   params_weight_decay_.push_back(spec ? static_cast<float>(spec->num("decay_mult", 1.0)) : 1.0f);
   // reference fault registry (net.cpp:482-493): InnerProduct weights + biases
   const std::string type = layers_[layer_id]->type();

@@ -21,6 +21,10 @@ void BlobFromProto(Blob<Dtype>* b, const BlobProtoData& p);  // shape-checked by
 template <typename Dtype>
 BlobProtoData BlobToProto(Blob<Dtype>* b, bool write_diff);
 
+// The lr_mult Net records for blob `param_id` of a layer: its `param` spec's
+// (default 1), else what the layer fixes (Layer::fixed_lr_mult), else 1.
+float ParamLrMult(const Layer<float>& layer, const Msg& layer_param, int param_id);
+
 template <typename Dtype>
 class Net {
  public:

@@ -198,6 +198,19 @@ SIGNATURES = {
     "rram_accuracy_groups_kernel_ids": (I, [I, I, I, I, I, I, C.c_char_p, SZ]),
     "rram_layer_entry_kernel_ids": (I, [I, I64, C.c_char_p, SZ]),
     "rram_layer_kernel_list": (I, [C.c_char_p, SZ]),
+    "rram_norm_workspace_floats": (SZ, [I, I, I64]),
+    "rram_bn_stats_train": (I, [P, I, I, I64, F, F, P, P, P, P, P, P, SZ, P]),
+    "rram_bn_stats_global": (I, [P, P, P, I, F, P, P, P]),
+    "rram_norm_apply": (I, [P, P, P, P, P, P, P, I, I, I, I64, P]),
+    "rram_norm_bwd_reduce": (I, [P, P, P, I, I, I64, P, P, P, P, P, P, SZ, P]),
+    "rram_norm_bwd_apply": (I, [P, P, P, P, P, P, P, I, I, I64, P]),
+    "rram_sigmoid_fwd": (I, [P, P, I64, P]),
+    "rram_sigmoid_bwd": (I, [P, P, P, I64, P]),
+    "rram_bn_fwd_kernel_ids": (I, [I, I, I64, I, I, I, C.c_char_p, SZ]),
+    "rram_bn_bwd_kernel_ids": (I, [I, I, I64, I, I, I, I, C.c_char_p, SZ]),
+    "rram_scale_kernel_ids": (I, [I, I, I64, I, I, I, C.c_char_p, SZ]),
+    "rram_sigmoid_kernel_ids": (I, [I64, I, C.c_char_p, SZ]),
+    "rram_norm_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_dropout_fwd": (I, [P, P, P, I64, F, U64, U32, U64, P]),
     "rram_dropout_bwd": (I, [P, P, P, I64, F, P]),
     "rram_bias_add": (I, [P, P, I, I, I, P]),

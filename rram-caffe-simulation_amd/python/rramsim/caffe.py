@@ -25,6 +25,8 @@ SIGNATURES = {
     "rram_caffe_set_random_seed": (I, [U64]),
     "rram_caffe_synchronize": (I, []),
     "rram_net_create": (I, [C.c_char_p, I, C.c_char_p, PP]),
+    "rram_layer_type_registered": (I, [C.c_char_p]),
+    "rram_norm_layer_check": (I, [C.c_char_p, I, I, PF]),
     "rram_net_destroy": (I, [P]),
     "rram_net_forward": (I, [P, I, PF]),
     "rram_net_backward": (I, [P]),
@@ -188,6 +190,19 @@ def describe(prototxt: str, phase: str = "test") -> List[tuple]:
         name, typ, bots, tops = line.split("\t")
         out.append((name, typ, [b for b in bots.split(",") if b], [t for t in tops.split(",") if t]))
     return out
+
+
+def layer_type_registered(type_name: str) -> bool:
+    """Host-only: whether the layer registry holds the type."""
+    return bool(load().rram_layer_type_registered(type_name.encode()))
+
+
+def norm_layer_check(layer_prototxt: str, num_bottoms: int = 1, bottom_axes: int = 4) -> List[float]:
+    """Host-only: what a BatchNorm / Scale layer checks of its LayerParameter (the fields of one layer
+    message); raises RramError as Net construction would, returns a BatchNorm's three recorded lr_mult."""
+    lr = (C.c_float * 3)(-1.0, -1.0, -1.0)
+    check(load().rram_norm_layer_check(layer_prototxt.encode(), num_bottoms, bottom_axes, lr), "norm_layer_check")
+    return list(lr)
 
 
 def caffemodel_describe(path: str) -> List[tuple]:

@@ -187,6 +187,89 @@ def cifar10_full(train_batch=100, test_batch=100) -> str:
     return p.text()
 
 
+def _bn(p, name, bottom, top=None, specs=False):
+    d = dict(name=name, type="BatchNorm", bottom=bottom, top=top or name)
+    if specs:
+        d["param"] = [dict(lr_mult=0)] * 3
+    p.layer(**d)
+
+
+def _scale(p, name, blob, bias=True):
+    p.layer(name=name, type="Scale", bottom=blob, top=blob, scale_param=dict(bias_term=bias))
+
+
+def cifar10_full_sigmoid_bn(train_batch=100, test_batch=1000) -> str:
+    """examples/cifar10/cifar10_full_sigmoid_train_test_bn.prototxt: cifar10_full with bias-free
+    convolutions, each followed (after pool1 for the first) by BatchNorm and Sigmoid."""
+    p = _P("CIFAR10_full")
+    _data(p, mean=True, train_batch=train_batch, test_batch=test_batch, name="cifar")
+    g = lambda s: dict(type="gaussian", std=s)  # noqa: E731
+
+    def conv(name, bottom, n, std):
+        p.layer(name=name, type="Convolution", bottom=bottom, top=name, param=[dict(lr_mult=1)],
+                convolution_param=dict(num_output=n, pad=2, kernel_size=5, stride=1, bias_term=False,
+                                       weight_filler=g(std)))
+
+    def sigmoid(name, bottom):
+        p.layer(name=name, type="Sigmoid", bottom=bottom, top=name)
+
+    conv("conv1", "data", 32, 0.0001)
+    _pool(p, "pool1", "conv1", "MAX", 3, 2)
+    _bn(p, "bn1", "pool1", specs=True)
+    sigmoid("Sigmoid1", "bn1")
+    conv("conv2", "Sigmoid1", 32, 0.01)
+    _bn(p, "bn2", "conv2", specs=True)
+    sigmoid("Sigmoid2", "bn2")
+    _pool(p, "pool2", "Sigmoid2", "AVE", 3, 2)
+    conv("conv3", "pool2", 64, 0.01)
+    _bn(p, "bn3", "conv3", specs=True)
+    sigmoid("Sigmoid3", "bn3")
+    _pool(p, "pool3", "Sigmoid3", "AVE", 3, 2)
+    _ip(p, "ip1", "pool3", 10, wf=g(0.01), param=[dict(lr_mult=1, decay_mult=1), dict(lr_mult=1, decay_mult=0)])
+    _heads(p, "ip1")
+    return p.text()
+
+
+VGG11_PLAN = (64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M")
+
+
+def cifar10_vgg11(train_batch=100, test_batch=100, fc=1024) -> str:
+    """The net the reference's fault experiment trains (usage.md, run_gaussian_exp.py): its solver template
+    examples/cifar10/gaussian_failure/solvers/cifar10_vgg11_template.prototxt names
+    cifar10_vgg11_fc1024_bn_scale_msra_fc_also.prototxt, and the reference ships no such file.  This is a
+    reconstruction from that file name alone: VGG11's convolution plan on 32x32 inputs (3x3, pad 1; "M" = 2x2
+    max pool, stride 2), a classifier of two fc layers of `fc` outputs and fc10, BatchNorm + in-place Scale
+    (with bias) + in-place ReLU after every convolution and after the two hidden fc layers ("fc_also"), MSRA
+    weight fillers throughout.  Layer names, multipliers and anything else the file may have held are this
+    project's choice, and no accuracy of the reference's is pinned to it."""
+    p = _P("CIFAR10_vgg11")
+    _data(p, mean=True, train_batch=train_batch, test_batch=test_batch, name="cifar")
+    msra = dict(type="msra")
+
+    def bn_scale_relu(i, blob):
+        _bn(p, f"bn{i}", blob, top=f"bn{i}")
+        _scale(p, f"scale{i}", f"bn{i}")
+        _relu(p, f"relu{i}", f"bn{i}")
+        return f"bn{i}"
+
+    bottom, ci, pi = "data", 0, 0
+    for step in VGG11_PLAN:
+        if step == "M":
+            pi += 1
+            _pool(p, f"pool{pi}", bottom, "MAX", 2, 2)
+            bottom = f"pool{pi}"
+        else:
+            ci += 1
+            _conv(p, f"conv{ci}", bottom, step, 3, pad=1, wf=msra, param=W1B2)
+            bottom = bn_scale_relu(ci, f"conv{ci}")
+    for j in (1, 2):
+        _ip(p, f"fc{j}", bottom, fc, wf=msra, param=W1B2)
+        bottom = bn_scale_relu(f"_fc{j}", f"fc{j}")
+    _ip(p, "fc3", bottom, 10, wf=msra, param=W1B2)
+    _heads(p, "fc3")
+    return p.text()
+
+
 def alexnet(train_batch=256, test_batch=256, caffenet=False) -> str:
     """models/bvlc_alexnet/train_val.prototxt (C3); caffenet=True gives
     models/bvlc_reference_caffenet/train_val.prototxt (pool before norm).
@@ -354,8 +437,15 @@ CONFIGS = {
 }
 
 
+# the BatchNorm nets of the fault experiment (not benchmark configs: CONFIGS is the benchmark's table)
+BN_CONFIGS = {
+    "cifar10_full_sigmoid_bn": (cifar10_full_sigmoid_bn, "3,32,32", 10),
+    "cifar10_vgg11": (cifar10_vgg11, "3,32,32", 10),
+}
+
+
 def net_options(name: str, **extra):
-    _, shape, classes = CONFIGS[name]
+    _, shape, classes = CONFIGS[name] if name in CONFIGS else BN_CONFIGS[name]
     o = dict(data_shape=shape, num_classes=classes)
     o.update(extra)
     return o

@@ -601,6 +601,93 @@ def layer_kernel_list():
     return buf.value.decode().split()
 
 
+# ---- BatchNorm / Scale / Sigmoid (csrc/norm.hip); tensors are (num, channels, inner...) float32 ----
+def _nci(x):
+    num, ch = x.shape[0], x.shape[1]
+    return num, ch, x.numel() // (num * ch)
+
+
+def norm_workspace_floats(num, channels, inner):
+    return int(_lib().rram_norm_workspace_floats(num, channels, inner))
+
+
+def bn_stats_train(x, mean, rstd, ws, eps=1e-5, maf=0.999, run_mean=None, run_var=None, factor=None):
+    """Per-channel mean and 1 / sqrt(biased var + eps) of x, plus the running update of the three
+    BatchNorm blobs when they are given (rram_bn_stats_train)."""
+    K.check(_lib().rram_bn_stats_train(_p(x), *_nci(x), eps, maf, _p(mean), _p(rstd), _p(run_mean), _p(run_var),
+                                       _p(factor), _p(ws), ws.numel(), _stream()), "bn_stats_train")
+
+
+def bn_stats_global(run_mean, run_var, factor, mean, rstd, eps=1e-5):
+    K.check(_lib().rram_bn_stats_global(_p(run_mean), _p(run_var), _p(factor), run_mean.numel(), eps, _p(mean),
+                                        _p(rstd), _stream()), "bn_stats_global")
+
+
+def norm_apply(x, y, mean=None, rstd=None, gamma=None, beta=None, relu=False, xhat_out=None):
+    """y = relu?(gamma * ((x - mean) * rstd) + beta), each stage optional; y may be x (rram_norm_apply)."""
+    K.check(_lib().rram_norm_apply(_p(x), _p(y), _p(xhat_out), _p(mean), _p(rstd), _p(gamma), _p(beta), int(relu),
+                                   *_nci(x), _stream()), "norm_apply")
+
+
+def norm_bwd_reduce(dy, xhat, ws, relu_y=None, gamma=None, rstd=None, dgamma=None, dbeta=None, coef=None):
+    """dbeta += sum g, dgamma += sum g * xhat per channel, coef = (gamma * rstd, sum g / m, sum g xhat / m)
+    (rram_norm_bwd_reduce)."""
+    K.check(_lib().rram_norm_bwd_reduce(_p(dy), _p(relu_y), _p(xhat), *_nci(dy), _p(gamma), _p(rstd), _p(dgamma),
+                                        _p(dbeta), _p(coef), _p(ws), ws.numel(), _stream()), "norm_bwd_reduce")
+
+
+def norm_bwd_apply(dy, dx, relu_y=None, xhat=None, coef=None, gamma=None, rstd=None):
+    K.check(_lib().rram_norm_bwd_apply(_p(dy), _p(relu_y), _p(xhat), _p(coef), _p(gamma), _p(rstd), _p(dx),
+                                       *_nci(dy), _stream()), "norm_bwd_apply")
+
+
+def scale_fwd(x, y, gamma, beta=None):
+    """The stand-alone Scale layer: y = x * gamma[c] (+ beta[c])."""
+    norm_apply(x, y, gamma=gamma, beta=beta)
+
+
+def scale_bwd(x, dy, gamma, ws, dgamma=None, dbeta=None, dx=None):
+    """dgamma += sum dy * x, dbeta += sum dy, dx = dy * gamma (dx may be dy)."""
+    if dgamma is not None or dbeta is not None:
+        norm_bwd_reduce(dy, x, ws, dgamma=dgamma, dbeta=dbeta)
+    if dx is not None:
+        norm_bwd_apply(dy, dx, gamma=gamma)
+
+
+def sigmoid_fwd(x, y):
+    K.check(_lib().rram_sigmoid_fwd(_p(x), _p(y), x.numel(), _stream()), "sigmoid_fwd")
+
+
+def sigmoid_bwd(y, dy, dx):
+    K.check(_lib().rram_sigmoid_bwd(_p(y), _p(dy), _p(dx), y.numel(), _stream()), "sigmoid_bwd")
+
+
+def bn_fwd_kernel_ids(num, channels, inner, global_stats=False, x_off=0, y_off=0):
+    """e.g. ['bn_stats_plane<4>', 'bn_stats_finalize', 'norm_apply<4>']; *_off: floats past a 16-byte boundary."""
+    return _id_lines(_lib().rram_bn_fwd_kernel_ids, num, channels, inner, int(global_stats), x_off, y_off)
+
+
+def bn_bwd_kernel_ids(num, channels, inner, global_stats=False, scale=False, dy_off=0, dx_off=0):
+    return _id_lines(_lib().rram_bn_bwd_kernel_ids, num, channels, inner, int(global_stats), int(scale), dy_off,
+                     dx_off)
+
+
+def scale_kernel_ids(num, channels, inner, backward=False, x_off=0, y_off=0):
+    return _id_lines(_lib().rram_scale_kernel_ids, num, channels, inner, int(backward), x_off, y_off)
+
+
+def sigmoid_kernel_ids(n, backward=False):
+    return _id_lines(_lib().rram_sigmoid_kernel_ids, n, int(backward))
+
+
+def norm_kernel_list():
+    """Every id the launch sites of csrc/norm.hip can record."""
+    n = _lib().rram_norm_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_norm_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
 def fill_uniform(x, lo, hi, seed, sid=0):
     K.check(_lib().rram_fill_uniform(_p(x), x.numel(), lo, hi, seed, sid, _stream()), "fill")
 

@@ -51,8 +51,17 @@ def experiment_solver(template: str, mean: float, std: float, threshold: float =
     strategy; `remapping` = "order_file[,period[,start]]"; `genetic` =
     "prune_net,prune_model[,switch_time[,period[,start]]]"; `prob` >= 0 sets the
     stuck-at split to (prob, 100 - 2 prob, prob)."""
-    lines = [l for l in template.splitlines()
-             if not l.strip().startswith(("failure_pattern", "snapshot_prefix"))]
+    lines, depth = [], 0
+    for l in template.splitlines():
+        code = l.split("#", 1)[0]
+        if depth > 0:                   # inside a failure_pattern block that spans lines (the VGG11 template's)
+            depth += code.count("{") - code.count("}")
+            continue
+        if l.strip().startswith("failure_pattern"):
+            depth = max(0, code.count("{") - code.count("}"))
+            continue
+        if not l.strip().startswith("snapshot_prefix"):
+            lines.append(l)
     text = "\n".join(lines)
     fp = f"failure_pattern {{ mean: {mean} std: {std}"
     if prob >= 0:
