@@ -1,5 +1,6 @@
-// Remapping and genetic fault-tolerance strategies:
-// include/caffe/strategy.hpp:84-183, src/caffe/strategy.cpp:35-288.
+// The fault-tolerance strategies: factory and threshold (strategy.cpp:7-33),
+// remapping and genetic: include/caffe/strategy.hpp:34-183,
+// src/caffe/strategy.cpp:7-288.
 #include <algorithm>
 #include <fstream>
 #include <numeric>
@@ -8,6 +9,49 @@
 #include "solver.hpp"
 
 namespace caffe {
+
+// ============================================================ strategies
+template <typename Dtype>
+std::shared_ptr<FailureStrategy<Dtype>> FailureStrategy<Dtype>::CreateStrategy(
+    const Msg& param, std::shared_ptr<FailureMaker<Dtype>> fm, std::shared_ptr<Net<Dtype>> net,
+    const Solver<Dtype>* s) {
+  const std::string type = param.str("type");
+  if (type == "threshold") {
+    auto p = std::make_shared<ThresholdFailureStrategy<Dtype>>(param, fm, net, s);
+    p->reference_lr_index = param.boolean("rram_reference_lr_index", false);
+    return p;
+  }
+  if (type == "remapping") {
+    auto p = std::make_shared<RemappingFailureStrategy<Dtype>>(param, fm, net, s);
+    p->reference_compat = param.boolean("rram_reference_compat", false);
+    return p;
+  }
+  if (type == "genetic") {
+    auto p = std::make_shared<GeneticFailureStrategy<Dtype>>(param, fm, net, s);
+    p->reference_compat = param.boolean("rram_reference_compat", false);
+    return p;
+  }
+  throw Error("No strategy named `" + type + "` exists.");
+}
+
+template <typename Dtype>
+float ThresholdFailureStrategy<Dtype>::threshold_for(int i) const {
+  const auto& lr = this->net_->params_lr();
+  const int idx = reference_lr_index ? i : this->net_->failure_learnable_param_ids()[i];
+  CAFFE_CHECK(idx < (int)lr.size(), "params_lr index out of range");
+  // strategy.cpp:13-14: rate = params_lr * lr (fp32), threshold = threshold_ * rate
+  const float rate = static_cast<float>(lr[idx]) * static_cast<float>(this->solver_->GetLearningRate());
+  return threshold() * rate;
+}
+
+// strategy.cpp:7-33, on the device (no D2H/H2D round trip)
+template <typename Dtype>
+void ThresholdFailureStrategy<Dtype>::Apply() {
+  const auto& fps = this->net_->failure_learnable_params();
+  for (size_t i = 0; i < fps.size(); ++i)
+    RRAM_CALL(rram_threshold_strategy(fps[i]->mutable_gpu_diff(), fps[i]->count(), threshold_for((int)i), nullptr,
+                                      Caffe::stream()));
+}
 
 // ================================================================ GlibcRand
 // srandom_r: r[0] = seed (0 -> 1), r[i] = 16807 r[i-1] mod (2^31 - 1) for
@@ -345,6 +389,8 @@ void GeneticFailureStrategy<Dtype>::Apply() {
   HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
 }
 
+template class FailureStrategy<float>;
+template class ThresholdFailureStrategy<float>;
 template class RemappingFailureStrategy<float>;
 template class GeneticFailureStrategy<float>;
 
