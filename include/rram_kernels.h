@@ -483,7 +483,9 @@ int rram_conv_octet_plan(const rram_conv_desc* d, int* plan);
  *                                   (tiles across images, per image, per image
  *                                   in whole output rows, whole images)
  *   c1x1<MI,NB,WR;vV>               1x1 register-ring kernel, V floats per load
- *   c1x1_dma<MI,NB,WR;vV>           1x1 LDS-DMA kernel
+ *                                   (V = 4 only with num_output <= 64, so only
+ *                                   on tiles of 32 MI WR <= 64 rows)
+ *   c1x1_dma<MI,NB,WR;v4>           1x1 LDS-DMA kernel (always 4 floats per load)
  *   patch<KH,CPH,MI,PD>             patch kernel
  *   conv1_ring<227>, conv_s2<NBW>   the two fixed-shape kernels
  *   f32                             no bf16x6 kernel: the fp32-MFMA implicit GEMM

@@ -351,15 +351,9 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
   const int wm = wave / WN;
   const int wn = wave % WN;
 
-  // XCD-aware tile order (cdna_hip_programming.md §5.5 T1, bijective form):
-  // dispatch deals blocks round-robin over 8 XCDs, so give every XCD a
-  // contiguous range of tiles; within it the m-tiles of one n-tile are
-  // adjacent (they share the B panel) and consecutive n-tiles follow.
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  // XCD-aware tile order: within an XCD's range the m-tiles of one n-tile
+  // are adjacent (they share the B panel) and consecutive n-tiles follow.
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   // integer division by a runtime divisor is expanded on the VALU; pin the
   // (block-uniform) results to SGPRs so the operand pointers and the buffer
   // descriptor derived from them stay scalar
@@ -784,11 +778,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   const int lr = lane & 31, lh = lane >> 5;
 
   // XCD-aware tile order, as k_gemm
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane((tid / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(tid / (P.tiles_m * P.tiles_n));
@@ -992,11 +982,7 @@ k_conv_patch(Params P, const float* __restrict__ wpack, int PW, int CS) {
   const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 31, lh = lane >> 5;
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane((tid / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(tid / (P.tiles_m * P.tiles_n));

@@ -60,6 +60,18 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t x, const FastDiv& f) {
   return (t + x) >> f.s;
 }
 
+// XCD-aware tile order.  Workgroup bid of nwg runs on XCD bid & 7 (the
+// hardware deals workgroups round-robin over the 8 XCDs); the tile id it
+// returns makes consecutive tile ids (which share an operand panel) land on
+// one XCD and so in one L2.  XCD x owns a contiguous range of nwg / 8 ids, the
+// first nwg & 7 XCDs one more each (the remainder workgroups).  A bijection
+// of [0, nwg).
+__device__ __forceinline__ int xcd_tile_id(int bid, int nwg) {
+  const int xcd = bid & 7, loc = bid >> 3;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+}
+
 // Operand view: element (row, k).
 struct View {
   const float* p;

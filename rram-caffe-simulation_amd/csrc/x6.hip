@@ -86,11 +86,7 @@ k_conv_patch_x6(Params P, const uint16_t* __restrict__ wpack, int PW, int CS) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 31, lh = lane >> 5;
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane((tid / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(tid / (P.tiles_m * P.tiles_n));
@@ -351,11 +347,7 @@ k_conv_cb_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* __r
   const int lr = lane & 31, lh = lane >> 5;
   const int wr = wave % WR, wc = wave / WR;
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane((tid / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(tid / (P.tiles_m * P.tiles_n));
@@ -1295,11 +1287,7 @@ k_conv1x1_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __rest
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 31, lh = lane >> 5;
   const int wr = wave % WR, wc = wave / WR;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane(tid / P.tiles_m);
   const int m0 = tm * BMc, n0 = tn * BNc;
@@ -1411,11 +1399,12 @@ k_conv1x1_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __rest
 // kt + 1 is a hand-counted vmcnt (every wave issues the same number of
 // pieces, OOB dummies included), so no weight load issued after the next
 // activation tile forces that tile to land early (the register-ring form's
-// in-order vmcnt did: about one K-tile of latency hiding).
+// in-order vmcnt did: about one K-tile of latency hiding).  16-byte
+// activation loads only (conv_1x1_dma).
 namespace c1x1 {
 constexpr int NS = 4;  // LDS stages
 }  // namespace c1x1
-template <int MI, int NB, int WR, int VEC>
+template <int MI, int NB, int WR>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_conv1x1_dma_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __restrict__ x, uint32_t xrange,
                  uint32_t wrange, char* __restrict__ yoct, int cout8) {
@@ -1424,7 +1413,7 @@ k_conv1x1_dma_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __
   constexpr int NS = c1x1::NS;
   constexpr int A_BYTES = RBL * 3072, B_BYTES = 64 * BNc, STB = A_BYTES + B_BYTES;
   constexpr int NA = RBL * 3;                         // 1 KB weight pieces per K-tile
-  constexpr int PIECE_B = VEC == 4 ? 1024 : 256;      // bytes per activation piece
+  constexpr int PIECE_B = 1024;                       // bytes per activation piece (16 per lane)
   constexpr int NBP = B_BYTES / PIECE_B;
   constexpr int PA = (NA + 3) / 4, PB = (NBP + 3) / 4, PPW = PA + PB;
   static_assert(NS * STB + 1024 <= 160 * 1024, "LDS");
@@ -1436,11 +1425,7 @@ k_conv1x1_dma_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 31, lh = lane >> 5;
   const int wr = wave % WR, wc = wave / WR;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane(tid / P.tiles_m);
   const int m0 = tm * BMc, n0 = tn * BNc;
@@ -1458,14 +1443,14 @@ k_conv1x1_dma_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __
     alds[i] = ok ? static_cast<uint32_t>((a / 3 * 3 + a % 3) * 1024) : 0xFFFFFFFFu;
   }
   // activation piece q = wave + 4 i: floats q PIECE_B / 4 .. of the stage's
-  // [16][BNc] tile, this lane's VEC of them at element q PIECE_B / 4 + VEC lane
+  // [16][BNc] tile, this lane's 4 of them at element q PIECE_B / 4 + 4 lane
   uint32_t boff[PB], blds[PB];
 #pragma unroll
   for (int i = 0; i < PB; ++i) {
     const int q = wave + 4 * i;
     uint32_t off = 0x80000000u;
     if (q < NBP) {
-      const int e = q * (PIECE_B / 4) + lane * VEC;
+      const int e = q * (PIECE_B / 4) + lane * 4;
       const int c = e / BNc, n = n0 + (e - c * BNc);
       if (n < P.N) {
         const uint32_t img = fdiv(static_cast<uint32_t>(n), P.cv.howo);
@@ -1492,10 +1477,7 @@ k_conv1x1_dma_x6(Params P, const x6::bf16x8* __restrict__ wpack, const float* __
       const bool real = ok && blds[i] != 0xFFFFFFFFu;
       const uint32_t vo = real && boff[i] != 0x80000000u ? boff[i] + static_cast<uint32_t>(kt) * kstep : 0x80000000u;
       const uint32_t dst = real ? st + blds[i] : lds0 + static_cast<uint32_t>(NS * STB);
-      if constexpr (VEC == 4)
-        dma_b128(xrs, vo, dst);
-      else
-        dma_b32(xrs, vo, dst);
+      dma_b128(xrs, vo, dst);
     }
   };
   floatx16 acc[MI][NB];
@@ -2052,11 +2034,9 @@ k_conv_s2_x6(Params P, const x6::bf16x8* __restrict__ wpack, int tiles_per_img, 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 31, lh = lane >> 5;
-  // XCD-aware order: consecutive tiles (which share input rows) on one XCD
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int t = __builtin_amdgcn_readfirstlane((xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc);
-  if (t >= tiles) return;  // (uniform per workgroup; nwg == tiles)
+  // consecutive tiles share input rows
+  const int t = __builtin_amdgcn_readfirstlane(xcd_tile_id(blockIdx.x, gridDim.x));
+  if (t >= tiles) return;  // (uniform per workgroup; gridDim.x == tiles)
   const int img = t / tiles_per_img, sp0 = (t - img * tiles_per_img) * BN;
   const int HWo = P.cv.howo.d, OW = P.cv.Wo, H = P.cv.H, W = P.cv.W;
   const int f = sp0 / OW;
@@ -2322,11 +2302,7 @@ k_gemm_x6(Params P, const uint16_t* __restrict__ apack, int ktiles_all, int ktc)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 31, lh = lane >> 5;
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int tid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tid = xcd_tile_id(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tid % P.tiles_m);
   const int tn = __builtin_amdgcn_readfirstlane((tid / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(tid / (P.tiles_m * P.tiles_n));
@@ -3159,8 +3135,12 @@ int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, c
 struct C1Plan {
   int MI, NB, WR, VEC, tiles_m, tiles_n;
 };
-// (MI, NB, WR) instantiated for VEC = 4 and VEC = 1
+// (MI, NB, WR): each the DMA form (VEC = 4 only: conv_1x1_dma) and the ring
+// form with VEC = 1.  The ring form with VEC = 4 runs only where M <= 64
+// (else conv_1x1_dma takes it), and conv_1x1_plan gives such an M no tile of
+// 32 MI WR >= 128 rows (half of it would pad): c1x1_ring_v4.
 #define RRAM_C1X1_LIST(X) X(1, 2, 1) X(2, 1, 1) X(2, 2, 1) X(2, 1, 2) X(4, 1, 1) X(4, 2, 1) X(4, 1, 2) X(4, 2, 2)
+constexpr bool c1x1_ring_v4(int mi, int wr) { return 32 * mi * wr <= 64; }
 bool conv_1x1_plan(const rram_conv_desc* d, const float* x, C1Plan& pl) {
   if (d->kernel_h != 1 || d->kernel_w != 1 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 0 ||
       d->pad_w != 0 || d->dilation_h != 1 || d->dilation_w != 1 || d->group != 1)
@@ -3245,18 +3225,17 @@ int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, con
   const bool dma = conv_1x1_dma(pl, M);
 #define RRAM_X(mi, nb, wr)                                                                                  \
   if (pl.MI == mi && pl.NB == nb && pl.WR == wr) {                                                          \
-    if (dma && pl.VEC == 4)                                                                                 \
-      hipLaunchKernelGGL((k_conv1x1_dma_x6<mi, nb, wr, 4>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange,   \
+    if (dma)                                                                                                \
+      hipLaunchKernelGGL((k_conv1x1_dma_x6<mi, nb, wr>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange,      \
                          wrange, yo, cout8);                                                                \
-    else if (dma)                                                                                           \
-      hipLaunchKernelGGL((k_conv1x1_dma_x6<mi, nb, wr, 1>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange,   \
-                         wrange, yo, cout8);                                                                \
-    else if (pl.VEC == 4)                                                                                   \
+    else if (pl.VEC == 1)                                                                                   \
+      hipLaunchKernelGGL((k_conv1x1_x6<mi, nb, wr, 1>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange, yo,   \
+                         cout8);                                                                            \
+    else if constexpr (c1x1_ring_v4(mi, wr))                                                                \
       hipLaunchKernelGGL((k_conv1x1_x6<mi, nb, wr, 4>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange, yo,   \
                          cout8);                                                                            \
     else                                                                                                    \
-      hipLaunchKernelGGL((k_conv1x1_x6<mi, nb, wr, 1>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange, yo,   \
-                         cout8);                                                                            \
+      return 0;                                                                                             \
   } else
   RRAM_C1X1_LIST(RRAM_X) { return 0; }
 #undef RRAM_X
@@ -3389,13 +3368,14 @@ std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16) {
   C1Plan c1;
   // (the plan only looks at the pointer's low bits: 4 = aligned to 4 bytes, not 16)
   if (conv_1x1_plan(d, x_align16 ? nullptr : reinterpret_cast<const float*>(uintptr_t{4}), c1)) {
+    const bool dma = conv_1x1_dma(c1, d->num_output);
     bool inst = false;
-#define RRAM_X(mi, nb, wr) inst = inst || (c1.MI == mi && c1.NB == nb && c1.WR == wr);
+#define RRAM_X(mi, nb, wr) \
+  inst = inst || (c1.MI == mi && c1.NB == nb && c1.WR == wr && (dma || c1.VEC == 1 || c1x1_ring_v4(mi, wr)));
     RRAM_C1X1_LIST(RRAM_X)
 #undef RRAM_X
     if (inst) {
-      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>", conv_1x1_dma(c1, d->num_output) ? "c1x1_dma" : "c1x1", c1.MI, c1.NB,
-               c1.WR, c1.VEC);
+      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>", dma ? "c1x1_dma" : "c1x1", c1.MI, c1.NB, c1.WR, c1.VEC);
       return b;
     }
   }
@@ -3435,11 +3415,12 @@ std::string conv_fwd_kernel_list() {
   RRAM_CB16_LIST(RRAM_X)
 #undef RRAM_X
 #define RRAM_X(mi, nb, wr)                                                            \
-  for (const char* f : {"c1x1", "c1x1_dma"})                                          \
-    for (int v : {4, 1}) {                                                            \
-      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>\n", f, mi, nb, wr, v);                  \
-      out += b;                                                                       \
-    }
+  if (c1x1_ring_v4(mi, wr)) {                                                         \
+    snprintf(b, sizeof b, "c1x1<%d,%d,%d;v4>\n", mi, nb, wr);                         \
+    out += b;                                                                         \
+  }                                                                                   \
+  snprintf(b, sizeof b, "c1x1<%d,%d,%d;v1>\nc1x1_dma<%d,%d,%d;v4>\n", mi, nb, wr, mi, nb, wr); \
+  out += b;
   RRAM_C1X1_LIST(RRAM_X)
 #undef RRAM_X
 #define RRAM_X(kh, cph, pd)                                            \

@@ -106,13 +106,6 @@ def reason(kid, above):
         fl, cs, _ = above[kid]
         return (f"selected only above the 2 GFLOP cap on a case: cheapest in the box x={cs['x']} cout={cs['cout']} "
                 f"k={cs['k']} p={cs['p']} g={cs['g']} at {fl / 1e9:.2f} GFLOP")
-    if fam == "c1x1_dma" and kid.endswith("v1>"):
-        return "never launched: the LDS-DMA form is taken only with 16-byte loads (conv_1x1_dma: VEC == 4)"
-    if fam == "c1x1" and kid.endswith("v4>"):
-        mi, _, wr = (int(v) for v in kid[5:kid.index(";")].split(","))
-        if 32 * mi * wr >= 128:
-            return ("never launched: a tile of >= 128 rows needs num_output > 64 (conv_1x1_plan), where 16-byte loads "
-                    "take the LDS-DMA form (conv_1x1_dma)")
     box = XC.SEARCH_BOX["cb/cb16" if fam in ("cb", "cb16") else "c1x1" if fam.startswith("c1x1") else "patch"]
     return "the planner chose it for no shape of the box: " + box
 

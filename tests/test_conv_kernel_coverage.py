@@ -5,6 +5,7 @@ ops.conv_fwd_kernel_id asks the launch paths' own plan functions, so a planner
 change that moves a shape to another kernel, or a new instantiation that no
 test shape runs, fails here; tests/test_gpu_conv_kernel_matrix.py then runs
 every entry of the same table against fp64."""
+import itertools
 import re
 
 import pytest
@@ -31,12 +32,34 @@ def test_case_selects_its_kernel(cs):
 
 
 def test_kernel_list_is_the_instantiated_set():
-    """10 + 3 x 2 channel-octet, 8 x {ring, dma} x {v4, v1} 1x1, 9 x 2 patch, 2 fixed."""
+    """10 + 3 x 2 channel-octet, 8 dma v4 + 8 ring v1 + 3 ring v4 1x1, 9 x 2 patch, 2 fixed."""
     from rramsim import ops
     ids = ops.conv_fwd_kernel_list()
-    assert len(ids) == len(set(ids)) == 10 + 6 + 32 + 18 + 2
+    assert len(ids) == len(set(ids)) == 10 + 6 + 19 + 18 + 2
     for k in ids:
         assert re.fullmatch(r"(cb|cb16|c1x1|c1x1_dma|patch|conv1_ring|conv_s2)<[0-9,]+(;[kv][0-9])?>", k), k
+
+
+def test_1x1_planner_selects_only_built_forms():
+    """The 1x1 forms that are not built are the ones the host cannot select:
+    the LDS-DMA form needs 16-byte loads (conv_1x1_dma), and with 16-byte loads
+    the register ring is left num_output <= 64, for which conv_1x1_plan takes
+    no tile of 32 MI WR >= 128 rows.  A sweep over num_output (every tile-row
+    threshold and the DMA threshold included), HW % 4 both ways and both input
+    alignments must never select a missing form (the id would read "f32")."""
+    from rramsim import ops
+    built = set(ops.conv_fwd_kernel_list())
+    for (h, w), n, al in itertools.product([(7, 4), (7, 7), (15, 15), (14, 17)], (1, 8), (True, False)):
+        for m in range(1, 521):
+            kid = ops.conv_fwd_kernel_id(ops.conv_desc((n, 16, h, w), m, 1, 1, 0, 1, 1), al)
+            where = (n, h, w, m, al, kid)
+            assert kid.startswith("c1x1"), where
+            assert strip_kind(kid) in built, where
+            mi, _, wr = (int(v) for v in kid[kid.index("<") + 1:kid.index(";")].split(","))
+            if family(kid) == "c1x1_dma":
+                assert not kid.endswith("v1>"), where
+            elif kid.endswith("v4>"):
+                assert 32 * mi * wr <= 64, where
 
 
 def test_every_instantiation_has_a_case_or_a_reason():
