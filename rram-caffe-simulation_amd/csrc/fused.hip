@@ -37,25 +37,11 @@ namespace {
 // pooled-output fold, Net::Net: its one reader takes the companion).
 constexpr int kBandPix = 512;  // input pixels per band (PPT = 2 per thread)
 // target grid of the LRN + pool band kernel: several block waves of 256 CUs
-#ifndef RRAM_LRN_BLOCKS
-#define RRAM_LRN_BLOCKS 4096
-#endif
-#ifndef RRAM_LRN_ALT
-#define RRAM_LRN_ALT 0
-#endif
-#ifndef RRAM_LRN_BAL  // even band heights (A/B builds: 0 = the tallest bands first)
-#define RRAM_LRN_BAL 1
-#endif
-#ifndef RRAM_LRN_YNT  // cache policy of the pooled y stores (A/B builds: 2 = nontemporal)
-#define RRAM_LRN_YNT 0
-#endif
-#ifndef RRAM_LRN_DIAG
-#define RRAM_LRN_DIAG 0
-#endif
-#ifndef RRAM_LRN_XCD
-#define RRAM_LRN_XCD 1
-#endif
-constexpr int kLrnBlocks = RRAM_LRN_BLOCKS;
+// (2048 measured the same within noise, profiles/r05_ab_lrn_walk.txt)
+constexpr int kLrnBlocks = 4096;
+// cache policy of the pooled y stores: default (2 = nontemporal cost norm1
+// +3 us, profiles/r05_ab_lrn_walk.txt r05o)
+constexpr int kLrnYPolicy = 0;
 constexpr int kLrnG = 2;
 
 // G channels per barrier (kLrnG = 2: measured on MI355X for both AlexNet
@@ -118,7 +104,7 @@ __global__ void __launch_bounds__(256)
   const int total = bands * chunks * static_cast<int>(gridDim.y);  // gridDim.y = images
   const int L = blockIdx.x + static_cast<int>(gridDim.x) * blockIdx.y;
   const int xq = total / 8, xr = total % 8, xcd = L % 8, xk = L / 8;
-  const int tile = !RRAM_LRN_XCD ? L : xcd < xr ? xcd * (xq + 1) + xk : xr * (xq + 1) + (xcd - xr) * xq + xk;
+  const int tile = xcd < xr ? xcd * (xq + 1) + xk : xr * (xq + 1) + (xcd - xr) * xq + xk;
   const int band = tile % bands, rest = tile / bands;
   const int n = rest / chunks;
   const int cb = (rest - n * chunks) * CC;
@@ -234,20 +220,14 @@ __global__ void __launch_bounds__(256)
     for (int d = 0; d < D; ++d) {
       // lrn_sq_add / lrn_scale / lrn_out (the unfused kernels' arithmetic) on
       // both pixels at once
-#if RRAM_LRN_DIAG == 1  // diagnostic builds only: no LRN arithmetic
-      const f32x2 v = w[d + PRE];
-#else
       const f32x2 v = lrn_value2<SIZE>(w + d, alpha_over_size, beta, k);
-#endif
       if (own0) yb[d][sl0] = v.x;
       if (own1) yb[d][sl1] = v.y;
     }
-#if RRAM_LRN_DIAG != 3  // diagnostic builds only: no barrier (garbage values)
     __syncthreads();
-#endif
     // pool the group's D channels (MaxPoolForward: -FLT_MAX start, strict ">"
     // in row-major window order over the taps inside the image)
-    const int nd = RRAM_LRN_DIAG == 2 ? 0 : min(D, ce - c0);  // DIAG 2: no pooling
+    const int nd = min(D, ce - c0);
 #pragma unroll
     for (int i = 0; i < MAXI; ++i) {
       const int d = it_d[i];
@@ -259,8 +239,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
           for (int a = 0; a < K; ++a)
 #pragma unroll
-            for (int b = 0; b < K; ++b)  // DIAG 5: no tap reads
-              t[a * K + b] = RRAM_LRN_DIAG == 5 ? __builtin_bit_cast(float, it_l[i] + a + b) : yl[rowbase(a) + (b & 1) * HWC + (b >> 1)];
+            for (int b = 0; b < K; ++b) t[a * K + b] = yl[rowbase(a) + (b & 1) * HWC + (b >> 1)];
           // v_max3 over the taps: the strict-">" walk's value whenever the
           // maximum is not zero (a quiet NaN loses to any number in both; the
           // plane holds products, never a signalling NaN); for a zero maximum
@@ -268,7 +247,7 @@ __global__ void __launch_bounds__(256)
           // -0, so such a window is walked again in order
 #pragma unroll
           for (int j = 0; j < K * K; j += 2) mv = max3f(mv, t[j], t[j + 1 < K * K ? j + 1 : j]);
-          if (RRAM_LRN_DIAG != 6 && mv == 0.0f) {  // DIAG 6: no in-order re-walk
+          if (mv == 0.0f) {
             mv = -FLT_MAX;
 #pragma unroll
             for (int j = 0; j < K * K; ++j) mv = t[j] > mv ? t[j] : mv;
@@ -284,9 +263,9 @@ __global__ void __launch_bounds__(256)
               if (ok && v > mv) mv = v;
             }
         }
-        if (RRAM_LRN_DIAG != 4 && ys)  // DIAG 4: no y store
+        if (ys)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, mv), yrs, it_vo[i], c0 * PHW * 4,
-                                                RRAM_LRN_YNT);
+                                                kLrnYPolicy);
         if (OCT) obuf[(c0 + d) & 7][it_out[i] - pr0 * PW] = mv;
       }
     }
@@ -362,14 +341,10 @@ __global__ void __launch_bounds__(256)
       step(std::integral_constant<int, 7>{});
     }
   };
-  // Odd channel chunks walk down (RRAM_LRN_ALT): chunk i's last halo channels
-  // and chunk i + 1's first ones are then the same channels read at the same
-  // time (both at the chunks' shared boundary, start or end of the walk), so
-  // the second read can merge in the XCD's L2 instead of going to memory
-  if (RRAM_LRN_ALT && (((rest - n * chunks) & 1) != 0))
-    walk(std::true_type{});
-  else
-    walk(std::false_type{});
+  // every chunk walks up (odd chunks walking down, so that neighbouring
+  // chunks read their shared halo channels at the same time, saved 20 MB of
+  // fetches per plane and no time: profiles/r05_ab_lrn_walk.txt r05q)
+  walk(std::false_type{});
 }
 
 }  // namespace
@@ -413,8 +388,8 @@ int rram_lrn_maxpool_fwd_octets(const float* x, float* y, void* y_oct, int num, 
   while (rb < PH && fits(rb + 1)) ++rb;
   // the fewest bands at that height, then their rows evened out (AlexNet
   // norm2: 7 + 6 pooled rows, not 8 + 5, so no block carries 1.5x another's
-  // pixels)
-  if (RRAM_LRN_BAL) rb = (PH + (PH + rb - 1) / rb - 1) / ((PH + rb - 1) / rb);
+  // pixels: norm2 73 -> 67.5 us, profiles/r05_ab_lrn_walk.txt r05p)
+  rb = (PH + (PH + rb - 1) / rb - 1) / ((PH + rb - 1) / rb);
   // channel chunks: as few as give >= kLrnBlocks blocks (each chunk re-reads
   // SIZE - 1 halo channels), equal sizes in multiples of 8 (2 * G without octets)
   const int step = y_oct ? 8 : 2 * kLrnG;

@@ -315,15 +315,11 @@ __device__ __forceinline__ void store_tile(const Loader<ROWS, KB>& L, float* lds
 // Occupancy target 4 waves per SIMD: the 128 x 128 / KB = 16 conv tile then
 // keeps its accumulators in VGPRs (116 VGPRs, no AGPRs, no spills) instead of
 // 80 VGPRs + 64 AGPRs at 3 waves; 4 blocks x 40 KB fill the 160 KB LDS.
-// Measured on MI355X (scripts/gpu_variants.sh): AlexNet b256 GEMMs 3.760 ->
-// 3.667 ms.  RRAM_V_WPE_OFF builds the compiler's own choice for A/B runs.
-#ifndef RRAM_V_WPE_OFF
-// wave tiles of more than 4 accumulators (MI * NI > 4) need > 128 VGPRs: they
-// target 2 waves per SIMD instead of spilling
+// Measured on MI355X (profiles/r01_gemm_sweep.txt): AlexNet b256 GEMMs 3.760
+// -> 3.667 ms against the compiler's own choice (3 waves).
+// Wave tiles of more than 4 accumulators (MI * NI > 4) need > 128 VGPRs: they
+// target 2 waves per SIMD instead of spilling.
 #define RRAM_GEMM_OCC __attribute__((amdgpu_waves_per_eu(MI * NI > 4 ? 2 : 4)))
-#else
-#define RRAM_GEMM_OCC
-#endif
 template <int WM, int WN, int MI, int NI, int AM, int BMODE, int OM, int KB>
 __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
   constexpr int BMr = WM * MI * 32;
@@ -337,12 +333,7 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
   // the LDS, so 4 blocks per CU instead of 2 hide the strided gather's latency
   // (MI355X: conv1 0.720 -> 0.672 ms).  The IP GEMMs measured slower that way
   // (VGPR spills at 4 waves) and the 16-deep tiles already fit 4 blocks.
-  // RRAM_V_DOUBLE keeps every kernel double-buffered for A/B runs.
-#ifndef RRAM_V_DOUBLE
   constexpr int NBUF = (KB == 32 && (BMODE == CONVT || BMODE == CONVT64)) ? 1 : 2;
-#else
-  constexpr int NBUF = 2;
-#endif
   __shared__ __attribute__((aligned(16))) float As[NBUF][BMr * LDK];
   __shared__ __attribute__((aligned(16))) float Bs[NBUF][BNr * LDK];
 
@@ -426,17 +417,6 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
     col.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vb.p), 0, P.cv.in_bytes, 0x00020000);
   }
 
-#ifdef RRAM_V_MFMA16
-  // v_mfma_f32_16x16x4_f32 variant: the wave tile as (2 MI) x (2 NI) 16x16 tiles
-  floatx4 acc[2 * MI][2 * NI];
-#pragma unroll
-  for (int i = 0; i < 2 * MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2 * NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-  const int l16 = threadIdx.x & 15, g16 = (threadIdx.x & 63) >> 4;
-#else
   floatx16 acc[MI][NI];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
@@ -444,7 +424,6 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
     for (int j = 0; j < NI; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-#endif
 
   Loader<BMr, KB> la;
   Loader<BNr, KB> lb;
@@ -462,18 +441,11 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
   }
   __syncthreads();
 
-#ifndef RRAM_V_MFMA16
   const int lr = lane & 31;
   const int lh = lane >> 5;
-#else
-  (void)lane;  // measured 6 % slower than the 32x32x2 form on AlexNet b256 (scripts/gpu_variants.sh)
-#endif
   for (int t = 0; t < ntiles; ++t) {
     const int cur = NBUF == 2 ? (t & 1) : 0;
     const bool more = (t + 1) < ntiles;
-#ifdef RRAM_V_PRIO
-    __builtin_amdgcn_s_setprio(1);
-#endif
     {
       // unconditional (no basic-block split): past the last tile every
       // element is out of range and the guarded loads return zeros
@@ -481,26 +453,6 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
       load_tile<AM, BMr, KB>(la, va, P.cv, col, m0, kn, kend);
       load_tile<BMODE, BNr, KB>(lb, vb, P.cv, col, n0, kn, kend);
     }
-#ifdef RRAM_V_MFMA16
-    // lane group g at step s of sub-block q uses k = 16q + 4g + s (A and B alike)
-#pragma unroll
-    for (int q = 0; q < KB / 16; ++q) {
-      float4 af[2 * MI], bf[2 * NI];
-#pragma unroll
-      for (int i = 0; i < 2 * MI; ++i)
-        af[i] = *reinterpret_cast<const float4*>(&As[cur][(wm * MI * 32 + i * 16 + l16) * LDK + q * 16 + g16 * 4]);
-#pragma unroll
-      for (int j = 0; j < 2 * NI; ++j)
-        bf[j] = *reinterpret_cast<const float4*>(&Bs[cur][(wn * NI * 32 + j * 16 + l16) * LDK + q * 16 + g16 * 4]);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int i = 0; i < 2 * MI; ++i)
-#pragma unroll
-          for (int j = 0; j < 2 * NI; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(pick(af[i], s4), pick(bf[j], s4), acc[i][j], 0, 0, 0);
-    }
-#else
 #pragma unroll
     for (int q = 0; q < KB / 16; ++q) {
       float4 af[MI][2], bf[NI][2];
@@ -527,30 +479,20 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
         }
       }
     }
-#endif
     // Interleave the next tile's global loads with the first MFMAs (a wave
     // issues VALU / VMEM while its MFMAs run): one load, then NMF MFMAs.
-#ifndef RRAM_V_NOSCHED
     {
       constexpr int NVM = vmem_per_tile<AM, BMr, KB>() + vmem_per_tile<BMODE, BNr, KB>();
       constexpr int NMF_TOT = MI * NI * KB / 2;
-#ifdef RRAM_V_SPREAD
-      constexpr int NMF = NMF_TOT / NVM > 0 ? NMF_TOT / NVM : 1;
-#else
       constexpr int NMF = NMF_TOT / (2 * NVM) > 0 ? NMF_TOT / (2 * NVM) : 1;
-#endif
 #pragma unroll
       for (int v = 0; v < NVM; ++v) {
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);    // VMEM read
         __builtin_amdgcn_sched_group_barrier(0x008, NMF, 0);  // MFMA
       }
     }
-#endif
     // the LDS writes of the staged tile stay behind every MFMA
     __builtin_amdgcn_sched_barrier(0);
-#ifdef RRAM_V_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     if (NBUF == 1) __syncthreads();  // every wave is done reading the single buffer
     if (more) {
       store_tile<AM, BMr, KB>(la, As[NBUF == 2 ? cur ^ 1 : 0]);
@@ -559,43 +501,7 @@ __global__ void __launch_bounds__(256) RRAM_GEMM_OCC k_gemm(Params P) {
     __syncthreads();
   }
 
-#ifdef RRAM_V_MFMA16
-  // epilogue: acc[i][j][r] -> row = 16 i + 4 g + r, col = 16 j + l16
-#pragma unroll
-  for (int j = 0; j < 2 * NI; ++j) {
-    const int n = n0 + wn * NI * 32 + j * 16 + l16;
-    if (n >= P.N) continue;
-    int64_t cbase = 0;
-    if (OM == OUT_NCHW && part == nullptr) {
-      const uint32_t im = fdiv(static_cast<uint32_t>(n), ep.hw);
-      const uint32_t s = static_cast<uint32_t>(n) - im * ep.hw.d;
-      cbase = (int64_t)im * ep.cimg + s;
-    }
-#pragma unroll
-    for (int i = 0; i < 2 * MI; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * MI * 32 + i * 16 + 4 * g16 + r;
-        if (m >= P.M) continue;
-        const float v = acc[i][j][r];
-        if (part != nullptr) {
-          part[(int64_t)m * P.N + n] = v;
-          continue;
-        }
-        float* dst = (OM == OUT_NCHW) ? (ep.C + cbase + (int64_t)m * ep.ldc)
-                                      : (ep.C + (int64_t)m * ep.ldc + n);
-        float o = ep.alpha * v;
-        if (ep.beta != 0.0f) o += ep.beta * *dst;
-        if (ep.bias_mode == RRAM_BIAS_ROW) o += ep.bias[m];
-        else if (ep.bias_mode == RRAM_BIAS_COL) o += ep.bias[n];
-        if (ep.relu) o = fmaxf(o, 0.0f);
-        *dst = o;
-      }
-    }
-  }
-#else
   gemm_epilogue<MI, NI, OM>(acc, P, ep, part, m0 + wm * MI * 32, n0 + wn * NI * 32, lr, lh);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1396,16 +1302,13 @@ template <int AM, int BMODE, int OM, int KB>
 int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
   if (pz <= 0) pz = gz;
   if (force_big) {
-#ifndef RRAM_SPLIT_THIN32
-#define RRAM_SPLIT_THIN32 1
-#endif
     // split-K grids with M <= 32 and N > 64 (the CIFAR-10 weight gradients:
     // Cout = 32, N = 76 / 801): 32 x 128 tiles, which waste no MFMA rows (64 x
     // 64 padded half): C4 0.362 -> 0.348 ms per iteration.  Not for N <= 64
     // (LeNet conv1, N = 26: 0.199 -> 0.204 ms, the 128-wide B tile gathers
     // mostly padding), profiles/r05_ab_split_thin32.txt
     if constexpr (KB == 32) {
-      if (RRAM_SPLIT_THIN32 && P.M <= 32 && P.N > 64) return launch_cfg<1, 4, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
+      if (P.M <= 32 && P.N > 64) return launch_cfg<1, 4, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
     }
     // split-K grids: 64 x 64 tiles when an operand is that thin (conv weight gradients)
     if (P.M <= 64 || P.N <= 64) return launch_cfg<2, 2, 1, 1, AM, BMODE, OM, KB>(P, gz, s);

@@ -689,33 +689,6 @@ __device__ __forceinline__ void conv_epilogue_nchw16(floatx4 (&acc)[MI][NJ], con
   }
 }
 
-// RRAM_CB_STAMP (diagnostic build only, never the product): per-group
-// s_memtime cycle sums of k_conv_cb16_x6 (slots 0 .. 2H:
-// the groups of an (even, odd) K-tile pair, 2H + 1: the end-of-K-tile
-// barriers, 2H + 2: the barrier after an odd K-tile's cross group, 2H + 3:
-// the prologue, 2H + 4: the epilogue, 2H + 5: wave-tiles), summed over waves
-// into g_cb_stamp (read by rram_debug_cb_stamps)
-#ifdef RRAM_CB_STAMP
-__device__ unsigned long long g_cb_stamp[64];
-__device__ __forceinline__ unsigned long long cb_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
-
-// RRAM_CB16_ABLATE (diagnostic builds only, wrong results), a bit mask of
-// the parts left out: 1 the K loop's B fragment reads (the MFMAs reuse the
-// prologue's), 2 its weight loads, 4 the next K-tile's patch staging (loads
-// and LDS stores), 8 its barriers, 16 the epilogue's stores.  Read with care:
-// stale operands (1, 2) and unwritten outputs (16: the layers after it then
-// multiply zeros) lower the chip's power and raise its clock, so part of
-// those savings is DVFS, not the removed work (profiles/r06_ab_cb16_ablate.txt)
-#ifndef RRAM_CB16_ABLATE
-#define RRAM_CB16_ABLATE 0
-#endif
 // KTO = KT & 1 (the K-tile count's parity, host-checked): one tail shape per
 // instantiation.  With both tails in one kernel (a runtime branch after the
 // K-tile pair loop) the register allocator could not keep the loop's values
@@ -732,22 +705,6 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
   constexpr int MI = 2, NJ = 2 * NB;
   static_assert(2 * SFB <= 160 * 1024, "LDS");
   static_assert(PP >= 2, "pair groups");
-#ifdef RRAM_CB_STAMP
-  constexpr bool STAMP = true;
-  __shared__ unsigned long long cst_lds[4][32];
-  if ((threadIdx.x & 63) < 32) cst_lds[threadIdx.x >> 6][threadIdx.x & 63] = 0;
-  unsigned long long ctprev = cb_stamp();
-  auto cstamp = [&](int slot) __attribute__((always_inline)) {
-    if constexpr (STAMP) {
-      const unsigned long long tn = cb_stamp();
-      if ((threadIdx.x & 63) == 0) cst_lds[threadIdx.x >> 6][slot] += tn - ctprev;
-      ctprev = tn;
-    }
-  };
-#define RRAM_CB_ST(slot) cstamp(slot)
-#else
-#define RRAM_CB_ST(slot)
-#endif
   __shared__ __attribute__((aligned(16))) char smem[2 * SFB];
   // the patch pieces' source offsets, one word per (piece, thread): read per
   // refill instead of held in PD registers (at two workgroups per CU the
@@ -909,12 +866,9 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
   // has >= 4 groups: the 3x3 forms (H = 4: +0.5 % maps/s, conv3 / conv4
   // -1 %, profiles/r05_ab_cb16_sd_band.txt) and, since H = 12 there, the
   // 5x5 form too (the r05 A/B's "5x5 keeps 1" described a build
-  // that never shipped; RRAM_CB16_SD5 = 1 is that variant: no difference,
+  // that never shipped; SD = 1 for the 5x5 form measured no difference,
   // profiles/r06_ab_conv_y_fold_sd5.txt)
-#ifndef RRAM_CB16_SD5
-#define RRAM_CB16_SD5 2
-#endif
-  constexpr int SD = KH == 5 ? RRAM_CB16_SD5 : (H >= 4 ? 2 : 1);
+  constexpr int SD = KH == 5 ? 2 : (H >= 4 ? 2 : 1);
   constexpr int PMAX = (PD + H - SD - 1) / (H - SD);  // patch pieces per group (the shortest K-tile spreads them over H - SD groups)
   static_assert(H >= 2, "pair groups");
   typedef int int4x __attribute__((ext_vector_type(4)));
@@ -984,7 +938,7 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
         constexpr int NKIND = ODD ? 0 : (gi + 1 < H ? 0 : 2);
         constexpr int NS0 = ODD ? 2 * gi : 2 * (gi + 1);
         const int q = q0 + gi;
-        if (MORE && !(RRAM_CB16_ABLATE & 4)) {
+        if (MORE) {
           if (gi >= SD) {
             constexpr int g0 = gi - SD;
 #pragma unroll
@@ -997,19 +951,16 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
                 int4x, __builtin_amdgcn_raw_buffer_load_b128(
                            xr, static_cast<int>(poff(i) + static_cast<uint32_t>(kt + 1) * 2u * PL), 0, 0));
         }
-        if ((gi + 1 < NG || MORE) && !(RRAM_CB16_ABLATE & 2)) load_a(fa[pa ^ 1], q + 1);
+        if (gi + 1 < NG || MORE) load_a(fa[pa ^ 1], q + 1);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const bool last = gi == NG - 1 && j == NJ - 1;
-          if (last && MORE && !(RRAM_CB16_ABLATE & 8)) {  // the next stage is complete
-            RRAM_CB_ST(ODD ? H + gi : gi);
+          if (last && MORE) {  // the next stage is complete
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            RRAM_CB_ST(2 * H + 1);
           }
-          if (RRAM_CB16_ABLATE & 1) {
-          } else if (!last) {
+          if (!last) {
             if (j + 1 < NJ)  // (the cross group: lower half from the stage before)
               read_b(fb[(j + 1) & 1], KIND == 1 ? oth : cur_st, cur_st, KIND, S0, j + 1);
             else
@@ -1030,20 +981,17 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
                                      x6::Parts{fb[j & 1][0], fb[j & 1][1], fb[j & 1][2]}, acc[i][j]);
           __builtin_amdgcn_sched_barrier(0);
         }
-        RRAM_CB_ST(ODD ? H + gi : gi);
         // every wave is past the cross group: the refill -- or, after the
         // tile's last K-tile, the next tile's patch -- may overwrite `oth`
-        if (ODD && gi == 0 && (MORE || more_tiles) && !(RRAM_CB16_ABLATE & 8)) {
+        if (ODD && gi == 0 && (MORE || more_tiles)) {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
           __builtin_amdgcn_sched_barrier(0);
-          RRAM_CB_ST(2 * H + 2);
         }
       });
     };
     using T_ = std::true_type;
     using F_ = std::false_type;
-    RRAM_CB_ST(2 * H + 3);
     int kt = 0;
     for (; kt + 2 < KT; kt += 2) {
       const int q0 = (kt / 2) * (2 * H + 1);
@@ -1079,19 +1027,8 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
       load_a_from(a_rsrc(nxt), fa[1], 0);
     }
     const int mwave = cur.m0 + 32 * wr, nwave = cur.n0 + wc * 32 * NB;
-    if (RRAM_CB16_ABLATE & 16) {  // keep the sums alive: one store under a condition never true at run time
-      float sum = 0.0f;
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sum += acc[i][j][r];
-      if (ep.relu == 12345 && ep.C != nullptr) ep.C[lane] = sum;
-      ep.C = nullptr;
-    }
     conv_epilogue_nchw16<MI, NJ>(acc, P, ep, mwave, nwave, c16, g, cur.plast + 1);
-    if (yoct != nullptr && !(RRAM_CB16_ABLATE & 16)) {
+    if (yoct != nullptr) {
       // the output's octet companion: lane group g holds rows 4 g .. 4 g + 3 of
       // both 16-row blocks; lanes g, g ^ 1 (lane ^ 16) trade one block so that
       // an even g stores octet g / 2 of block 0 and an odd g octet (g - 1) / 2
@@ -1122,11 +1059,6 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
         x6::store_terms8(v, yoct + (((int64_t)im * cout8 + oct) * HW + sp_) * 48);
       }
     }
-    RRAM_CB_ST(2 * H + 4);
-#ifdef RRAM_CB_STAMP
-    if constexpr (STAMP)
-      if ((threadIdx.x & 63) == 0) cst_lds[threadIdx.x >> 6][2 * H + 5] += 1;
-#endif
     if (!more_tiles) break;
     // the next tile's first weight group moves to fa[0]
 #pragma unroll
@@ -1137,13 +1069,7 @@ k_conv_cb16_x6(Params P, const x6::bf16x8* __restrict__ wpack, const uint16_t* _
     t = tnext;
     sp ^= KTO;
   }
-#ifdef RRAM_CB_STAMP
-  if constexpr (STAMP)
-    if ((threadIdx.x & 63) == 0)
-      for (int k = 0; k < 2 * H + 6; ++k) atomicAdd(&g_cb_stamp[k], cst_lds[threadIdx.x >> 6][k]);
-#endif
 }
-#undef RRAM_CB_ST
 
 // w [G*M][Cg][T] -> k_conv_cb16_x6 fragments [G][rblocks][NQ][2][term][64 lanes][8],
 // NQ = ceil(KT T / 2) groups in the kernel's K order: per (even, odd) pair
@@ -1616,37 +1542,10 @@ constexpr uint32_t hi_mask(int q) { return q >= NQ ? 0u : (q % KQ == KQ - 1 ? 0x
 constexpr uint32_t lo_mask(int q) { return q >= NQ ? 0u : 0xFFFFFFFFu; }
 }  // namespace c1x6
 
-// RRAM_C1_STAMP (diagnostic build only, never the product): per-group
-// s_memtime cycle sums of k_conv1_ring_x6 (slots 0 .. G - 1: group g's
-// compute, G .. G + 2: the three barriers, G + 3: per-tile setup, G + 4: tile
-// count), summed over waves into g_c1_stamp (read by rram_debug_c1_stamps)
-#ifdef RRAM_C1_STAMP
-__device__ unsigned long long g_c1_stamp[64];
-__device__ __forceinline__ unsigned long long c1_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img, int tiles) {
   using namespace c1x6;
-#ifdef RRAM_C1_STAMP
-  __shared__ unsigned long long st_lds[4][32];
-  if ((threadIdx.x & 63) < 32) st_lds[threadIdx.x >> 6][threadIdx.x & 63] = 0;
-  unsigned long long tprev = 0;
-  auto stamp_to = [&](int slot) __attribute__((always_inline)) {
-    const unsigned long long tn = c1_stamp();
-    if ((threadIdx.x & 63) == 0) st_lds[threadIdx.x >> 6][slot] += tn - tprev;
-    tprev = tn;
-  };
-#define RRAM_C1_ST(slot) stamp_to(slot)
-#else
-#define RRAM_C1_ST(slot)
-#endif
   constexpr int OW = (W - 11) / 4 + 1, MI = 3;
   static_assert(4 * (OW - 1) + 4 * KQ <= ROWE, "slot rows too short");
   __shared__ __attribute__((aligned(16))) char smem[3 * SLOTB];
@@ -1694,21 +1593,9 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
     // lands in private memory and every load becomes a waterfall loop)
     const __amdgpu_buffer_rsrc_t xrs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin), 0, in_bytes, 0x00020000);
-#ifdef RRAM_C1_LOAD128
-    // (A/B: two 16-byte loads at 4-byte alignment per chunk instead of eight 4-byte loads)
-    typedef float float4x __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float4x q = __builtin_bit_cast(
-          float4x, __builtin_amdgcn_raw_buffer_load_b128(xrs, static_cast<int>(voff + 16 * h), 0, 0));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[4 * h + e] = q[e];
-    }
-#else
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, static_cast<int>(voff + 4 * e), 0, 0));
-#endif
   };
   auto stage_store = [&](int c, int k, float (&v)[8]) {
     const int q = chunk_of(k);
@@ -1732,14 +1619,6 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
       stage_load(tr, c, k, sv[0]);
       stage_store(c, k, sv[0]);
     }
-  };
-  // spread refill: step 0 loads chunks 0, 1; step 1 stores them and loads 2, 3; step 2 stores 2, 3
-  static_assert(CPT <= 4, "refill schedule covers 4 chunks per thread");
-  // one register set u of refill step `step`: store the chunk it loaded in
-  // the previous step, then load its chunk of this step
-  auto refill_part = [&](const TileRef& tr, int c, int step, int u) __attribute__((always_inline)) {
-    if (step > 0 && 2 * (step - 1) + u < CPT) stage_store(c, 2 * (step - 1) + u, sv[u]);
-    if (step < 2 && 2 * step + u < CPT) stage_load(tr, c, 2 * step + u, sv[u]);
   };
 
   // the weight fragments are the same for every tile: the base address is
@@ -1795,10 +1674,6 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
   };
   auto tile_body = [&](auto cc, int t) __attribute__((always_inline)) {
     constexpr int CUR = decltype(cc)::value;
-#ifdef RRAM_C1_STAMP
-    tprev = c1_stamp();
-    if ((threadIdx.x & 63) == 0) st_lds[threadIdx.x >> 6][G + 4] += 1;
-#endif
     const TileRef cur = tile_ref(t), nxt = tile_ref(t + nwg);
     const int img = cur.img, sp0 = (t - img * tiles_per_img) * BN, f = cur.f;
     // per-lane slot byte offsets (term 0, quad 0) of this wave's two 32-column blocks
@@ -1852,45 +1727,31 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
     x6::Parts F[2][2];
 #pragma unroll
     for (int part = 0; part < 6; ++part) read_part(F[0], 0, part);
-    RRAM_C1_ST(G + 3);
     static_for<0, G>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       x6::Parts (&fc)[2] = F[g & 1];
       x6::Parts (&fn)[2] = F[(g + 1) & 1];
       if (g + 2 < G) load_a(fg[(g + 2) % 3], g + 2);
-      // slot refills (see the header): channel 2 of this tile at groups 1, 3, 5;
-      // channel 0 / 1 of the next tile two, four and six groups after their last reader
-#ifndef RRAM_C1_SPREAD
-#define RRAM_C1_SPREAD 1
-#endif
-#if !RRAM_C1_SPREAD
-      auto refill = [&](int u) __attribute__((always_inline)) {
-        // (unconditional: the first tile re-fills slot 2 with what the prologue
-        // put there; past the last tile the loads return zeros into dead slots)
-        if (g >= 1 && g <= 5 && (g & 1)) refill_part(cur, 2, (g - 1) / 2, u);
-        constexpr int d0 = g - last_group(0) - 1, d1 = g - last_group(1) - 1;
-        if (d0 >= 0 && d0 <= 4 && (d0 & 1) == 0) refill_part(nxt, 0, d0 / 2, u);
-        if (d1 >= 0 && d1 <= 4 && (d1 & 1) == 0) refill_part(nxt, 1, d1 / 2, u);
-      };
-#else
-      // round 6: one chunk per group over CPT + 1 consecutive groups per slot
-      // -- load chunk s at step s, store it at step s + 1 -- instead of two
-      // per step on every other group (RRAM_C1_SPREAD=0); the same windows:
-      // slot 2 before the barrier after group last_group(0), slots 0 / 1
-      // before the next barriers.  483 VGPRs and no scratch (was 512 + 20 B),
-      // conv1 -0.6 % (profiles/r06_ab_conv1.txt)
+      // slot refills (see the header): channel 2 of this tile from group 1,
+      // channel 0 / 1 of the next tile from the group after their last reader.
+      // One chunk per group over CPT + 1 consecutive groups per slot -- load
+      // chunk s at step s, store it at step s + 1 -- instead of round 5's two
+      // per step on every other group; the same windows: slot 2 before the
+      // barrier after group last_group(0), slots 0 / 1 before the next
+      // barriers.  483 VGPRs and no scratch (was 512 + 20 B), conv1 -0.6 %
+      // (profiles/r06_ab_conv1.txt)
       auto refill1 = [&](const TileRef& tr, int c, int st) __attribute__((always_inline)) {
         if (st > 0 && st - 1 < CPT) stage_store(c, st - 1, sv[(st - 1) & 1]);
         if (st < CPT) stage_load(tr, c, st, sv[st & 1]);
       };
-      auto refill = [&](int u) __attribute__((always_inline)) {
-        if (u != 0) return;
+      // (unconditional: the first tile re-fills slot 2 with what the prologue
+      // put there; past the last tile the loads return zeros into dead slots)
+      auto refill = [&]() __attribute__((always_inline)) {
         if (g >= 1 && g <= 1 + CPT) refill1(cur, 2, g - 1);
         constexpr int d0 = g - last_group(0) - 1, d1 = g - last_group(1) - 1;
         if (d0 >= 0 && d0 <= CPT) refill1(nxt, 0, d0);
         if (d1 >= 0 && d1 <= CPT) refill1(nxt, 1, d1);
       };
-#endif
 #pragma unroll
       for (int q = 0; q < 2 * MI; ++q) {
         const int i = q >> 1, j = q & 1;
@@ -1898,8 +1759,7 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
         ac[i][j] = x6::mfma6(x6::Parts{fa[0], fa[1], fa[2]}, fc[j], ac[i][j]);
         // the next group's B fragment part q under MFMA6 block q
         if (g + 1 < G) read_part(fn, g + 1, q);
-        if (q == 1) refill(0);
-        if (q == 4) refill(1);
+        if (q == 1) refill();
         // the previous tile's outputs: groups 0 .. 11, 8 values per group
         if (g < 12 && q == 3) store_part(ap_, g);
 #pragma unroll
@@ -1915,11 +1775,7 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
       }
       // barriers: after the last readers of channel 0 / 1 (their slots are then
       // refilled) and at the end of the tile
-      RRAM_C1_ST(g);
-      if (g == last_group(0) || g == last_group(1) || g == G - 1) {
-        lds_barrier();
-        RRAM_C1_ST(G + (g == last_group(0) ? 0 : g == last_group(1) ? 1 : 2));
-      }
+      if (g == last_group(0) || g == last_group(1) || g == G - 1) lds_barrier();
     });
     // this tile's output offsets, stored under the next tile (bias + ReLU:
     // conv_epilogue_nchw's arithmetic; the bias from LDS)
@@ -1935,10 +1791,6 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
     if (t + nwg >= tiles) {
 #pragma unroll
       for (int s8 = 0; s8 < 12; ++s8) store_part(acc[0], s8);
-#ifdef RRAM_C1_STAMP
-      if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < G + 5; ++k) atomicAdd(&g_c1_stamp[k], st_lds[threadIdx.x >> 6][k]);
-#endif
       return;
     }
     tile_body(std::integral_constant<int, 1>{}, t + nwg);
@@ -1947,12 +1799,7 @@ k_conv1_ring_x6(Params P, const uint16_t* __restrict__ wpack, int tiles_per_img,
 #pragma unroll
     for (int s8 = 0; s8 < 12; ++s8) store_part(acc[1], s8);
   }
-#ifdef RRAM_C1_STAMP
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < G + 5; ++k) atomicAdd(&g_c1_stamp[k], st_lds[threadIdx.x >> 6][k]);
-#endif
 }
-#undef RRAM_C1_ST
 
 // Weight repack for k_conv1_ring_x6: w [M][3][11][11] -> fragments
 // [27 groups][3 row blocks][3 terms][64 lanes][8 bf16]; lane (lr, h) of
@@ -2268,9 +2115,6 @@ __global__ void __launch_bounds__(256) k_conv_patch_pack_x6(const float* __restr
 // partial slabs reduced by k_splitk_reduce.
 // K order inside a K-tile: group g, lane half h holds k = 16 h + 8 g + j
 // (the B rows' 16-byte quads 4h + 2g + u, u = 0, 1, swizzled as k_gemm2).
-#ifndef RRAM_FC_ABLATE
-#define RRAM_FC_ABLATE 0
-#endif
 namespace gx6 {
 constexpr int KT = 32;
 constexpr int RLB = 2 * 96 + 16;  // packed A row bytes per K-tile ([g][h][term][8 bf16] + pad, RLB/16 odd)
@@ -2436,12 +2280,10 @@ k_gemm_x6(Params P, const uint16_t* __restrict__ apack, int ktiles_all, int ktc)
 #pragma unroll
           for (int e = 0; e < NVM; ++e)
             if ((e * NB) / NVM == q) {
-              // RRAM_FC_ABLATE (diagnostic builds only, wrong results): 1 drops
-              // the A pieces, 2 the B pieces of the K-tile loop
               if (e < A_DMA) {
-                if (RRAM_FC_ABLATE != 1) issue_a(t + 1, e);
+                issue_a(t + 1, e);
               } else if (more2) {
-                if (RRAM_FC_ABLATE != 2) issue_b(t + 2, e - A_DMA);
+                issue_b(t + 2, e - A_DMA);
               }
             }
         }
@@ -2645,12 +2487,12 @@ int conv_wide_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, co
 }
 
 // ---- k_conv_s2_x6 (GoogLeNet conv1: 3 channels, 64 x 7 x 7, stride 2) ----
-#ifndef RRAM_S2_NBW  // 32-column blocks per wave of k_conv_s2_x6 (2: 64 x 256 tiles, two per CU; 1: 64 x 128, three)
-#define RRAM_S2_NBW 2
-#endif
+// 32-column blocks per wave of k_conv_s2_x6: 64 x 256 tiles, two per CU
+// (1 = 64 x 128, three per CU, was 20 % slower: profiles/r06_ab_conv_s2_nbw.txt)
+constexpr int kS2Nbw = 2;
 bool conv_s2_ok(const rram_conv_desc* d) {
   namespace k = c7x6;
-  using T = k::Tile<RRAM_S2_NBW>;
+  using T = k::Tile<kS2Nbw>;
   return d->group == 1 && d->channels == k::C && d->kernel_h == k::KS && d->kernel_w == k::KS &&
          d->stride_h == k::S && d->stride_w == k::S && d->dilation_h == 1 && d->dilation_w == 1 && d->pad_h >= 0 &&
          d->pad_h <= 3 && d->pad_w >= 0 && d->pad_w <= 3 && d->num_output >= 1 && d->num_output <= k::BM &&
@@ -2704,12 +2546,12 @@ int conv_s2_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, cons
     const int rc = launch_status("conv s2 weight pack x6");
     if (rc) return rc;
   }
-  const int tpi = (HW + c7x6::Tile<RRAM_S2_NBW>::BN - 1) / c7x6::Tile<RRAM_S2_NBW>::BN;
+  const int tpi = (HW + c7x6::Tile<kS2Nbw>::BN - 1) / c7x6::Tile<kS2Nbw>::BN;
   const int64_t tiles = (int64_t)d->num * tpi;
   RRAM_REQUIRE(tiles < (1ll << 31), "conv: grid too large");
   // (a persistent form, one workgroup per CU with the weights in registers:
   // 0.61 vs 0.43 ms in the GoogLeNet map, profiles/r06_ab_conv_s2_persistent.txt)
-  hipLaunchKernelGGL(k_conv_s2_x6<RRAM_S2_NBW>, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, P,
+  hipLaunchKernelGGL(k_conv_s2_x6<kS2Nbw>, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, P,
                      reinterpret_cast<const x6::bf16x8*>(wp), tpi, static_cast<int>(tiles));
   const int rc = launch_status("conv s2 x6");
   return rc ? rc : 1;
@@ -2807,12 +2649,6 @@ bool cb_instantiated(int KH, int WR, int NB, int PD, int OCC = 1) {
 #undef RRAM_X
   return false;
 }
-#ifndef RRAM_CB_ROWALIGN  // 0: no row-aligned per-image tiles; 1: by the cost rule; 2: wherever they fit (A/B)
-#define RRAM_CB_ROWALIGN 1
-#endif
-#ifndef RRAM_CB_IMGALIGN  // 0: no octet plan for planes of < 64 positions
-#define RRAM_CB_IMGALIGN 1
-#endif
 // Planes of < 64 positions (GoogLeNet's 7 x 7 stage): 128 consecutive
 // positions would span 4 images (the patch holds 3 segments), so the tiles are
 // whole images -- tp = floor(128 / HW) images' positions per 128-column tile
@@ -2854,7 +2690,7 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
   const int G = d->group, Cg = d->channels / G, M = d->num_output / G;
   const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h, N = d->num * HW;
   if (Cg % 16 != 0 || M == 0) return false;
-  if (HW < 64) return RRAM_CB_IMGALIGN && conv_cb_plan_whole_images(d, pl);
+  if (HW < 64) return conv_cb_plan_whole_images(d, pl);
   const int PW = d->width + 2 * d->pad_w;
   // row pitch in 16-byte chunks: >= 3 PW, = 3 OW (mod 16) (bank-conflict-free reads)
   int RPC = 3 * PW;
@@ -2951,14 +2787,12 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
           }
           octb = (rmax * RPC * 16 + 255) / 256 * 256;
         } else {
-          if (!RRAM_CB_ROWALIGN || OW > BN || BN % OW == 0 || HW <= BN) continue;
+          if (OW > BN || BN % OW == 0 || HW <= BN) continue;
           // 64 x 128 tiles only: GoogLeNet conv2 0.875-0.886 ms there vs
           // 0.943-0.963 on 128 x 128 (a quarter of the rows padded; equal
           // estimates), profiles/r06_ab_cb_rowalign.txt
-#ifndef RRAM_CB_RA_WR
-#define RRAM_CB_RA_WR 2
-#endif
-          if (WR != RRAM_CB_RA_WR) continue;
+          constexpr int kRowAlignWR = 2;
+          if (WR != kRowAlignWR) continue;
           tp = BN / OW * OW;
           tpi = (HW + tp - 1) / tp;
           rmax = tp / OW + KH - 1;
@@ -2996,9 +2830,7 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
     // 1.5x: GoogLeNet conv2 (56 x 56, one-per-CU 64 x 256 before) 0.935-0.963
     // -> 0.856-0.886 ms at an estimate of 1.44x; where another two-per-CU plan
     // fits they measured slower (profiles/r06_ab_cb_rowalign.txt).
-    // RRAM_CB_ROWALIGN == 2 (A/B builds): the row-aligned plan wherever it fits
-    else if (best3 > 0 && ((best2 < 0 && best3 * 2 <= best * 3) || RRAM_CB_ROWALIGN == 2)) pl = p3;
-    if (RRAM_CB_ROWALIGN == 2 && best3 > 0) pl = p3;
+    else if (best3 > 0 && (best2 < 0 && best3 * 2 <= best * 3)) pl = p3;
   }
   return best > 0;
 }
@@ -3095,12 +2927,11 @@ int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, c
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-#ifndef RRAM_CB16_PERSIST_X2  // persistent while tiles <= slots * X2 / 2 (A/B builds)
-#define RRAM_CB16_PERSIST_X2 3
-#endif
+    // persistent while tiles <= 1.5 x the slots (AlexNet conv5); everywhere
+    // loses 6 % on conv2, nowhere 5 % on conv5: profiles/r06_ab_cb16_persistent.txt
+    constexpr int kPersistX2 = 3;
     const int64_t slots = (2 * cus) / 8 * 8;
-    const unsigned nwg16 =
-        static_cast<unsigned>(nwg * 2 <= slots * RRAM_CB16_PERSIST_X2 ? std::min<int64_t>(nwg, slots) : nwg);
+    const unsigned nwg16 = static_cast<unsigned>(nwg * 2 <= slots * kPersistX2 ? std::min<int64_t>(nwg, slots) : nwg);
 #define RRAM_X2(kh, wr, nb, pd, occ, kpar)                                                                          \
   if (KH == kh && pl.WR == wr && pl.NB == nb && pl.PD == pd && pl.OCC == occ && kto == kpar) {                      \
     hipLaunchKernelGGL((k_conv_cb16_x6<kh, kh, wr, nb, pd, occ, kpar>), dim3(nwg16), dim3(256), 0, s, P, wp, xp,      \
@@ -3381,7 +3212,7 @@ std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16) {
   }
   if (conv1_ring_ok(d)) return "conv1_ring<227>";
   if (conv_s2_ok(d)) {
-    snprintf(b, sizeof b, "conv_s2<%d>", RRAM_S2_NBW);
+    snprintf(b, sizeof b, "conv_s2<%d>", kS2Nbw);
     return b;
   }
   ConvPlan pp;
@@ -3431,7 +3262,7 @@ std::string conv_fwd_kernel_list() {
   RRAM_PATCH_LIST(RRAM_X)
 #undef RRAM_X
   out += "conv1_ring<227>\n";
-  snprintf(b, sizeof b, "conv_s2<%d>\n", RRAM_S2_NBW);
+  snprintf(b, sizeof b, "conv_s2<%d>\n", kS2Nbw);
   out += b;
   return out;
 }
@@ -3461,18 +3292,13 @@ bool gemm_x6_plan(int M, int N, int K, size_t ws_bytes, GemmPlan& pl) {
   pl.ktiles = (K + gx6::KT - 1) / gx6::KT;
   // split-K toward 256 workgroups, >= 8 K-tiles (256 k) per split
   const int64_t tiles = (int64_t)pl.tiles_m * pl.tiles_n;
-// (32 splits of >= 4 K-tiles, which moves fc8 onto this kernel, measured
-// 0.034 vs 0.032 ms on the fp32 engine: profiles/r05_ab_fc8_split32.txt)
-#ifndef RRAM_X6_SPLIT_MAX
-#define RRAM_X6_SPLIT_MAX 16
-#endif
-#ifndef RRAM_X6_MIN_KT
-#define RRAM_X6_MIN_KT 8
-#endif
+  // (32 splits of >= 4 K-tiles, which moves fc8 onto this kernel, measured
+  // 0.034 vs 0.032 ms on the fp32 engine: profiles/r05_ab_fc8_split32.txt)
+  constexpr int kSplitMax = 16, kMinKtiles = 8;
   int split = 1;
   if (ws_bytes > 0 && tiles < 256) {
-    split = static_cast<int>(std::min<int64_t>(RRAM_X6_SPLIT_MAX, 256 / tiles));
-    while (split > 1 && pl.ktiles / split < RRAM_X6_MIN_KT) --split;
+    split = static_cast<int>(std::min<int64_t>(kSplitMax, 256 / tiles));
+    while (split > 1 && pl.ktiles / split < kMinKtiles) --split;
     while (split > 1 && (size_t)split * M * N * sizeof(float) > ws_bytes) --split;
   }
   pl.ktc = (pl.ktiles + split - 1) / split;
@@ -3565,24 +3391,6 @@ int gemm_x6_nt(int M, int N, int K, float alpha, const float* A, int lda, const 
 
 extern "C" {
 
-#ifdef RRAM_CB_STAMP
-// diagnostic build only: the 3x3 octet-kernel stamp sums (and reset)
-int rram_debug_cb_stamps(unsigned long long* out, int n) {
-  if (out != nullptr && hipMemcpyFromSymbol(out, HIP_SYMBOL(rram::g_cb_stamp), sizeof(unsigned long long) * n) != hipSuccess)
-    return -2;
-  unsigned long long z[64] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(rram::g_cb_stamp), z, sizeof(z)) == hipSuccess ? 0 : -2;
-}
-#endif
-#ifdef RRAM_C1_STAMP
-// diagnostic build only: the conv1 stamp sums (and reset)
-int rram_debug_c1_stamps(unsigned long long* out, int n) {
-  if (out != nullptr && hipMemcpyFromSymbol(out, HIP_SYMBOL(rram::g_c1_stamp), sizeof(unsigned long long) * n) != hipSuccess)
-    return -2;
-  unsigned long long z[64] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(rram::g_c1_stamp), z, sizeof(z)) == hipSuccess ? 0 : -2;
-}
-#endif
 
 int rram_f32_engine_for_conv(const rram_conv_desc* d) {
   RRAM_REQUIRE(d != nullptr, "engine query: desc is NULL");

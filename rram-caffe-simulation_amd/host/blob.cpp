@@ -33,83 +33,43 @@ void* Caffe::workspace(size_t bytes) {
 
 void Caffe::synchronize() { HIP_CALL(hipStreamSynchronize(hip_stream())); }
 
+// Grows only: a larger request waits for the stream's readers of the old
+// buffer, frees it and tells the captured graphs (which hold its address,
+// Caffe::scratch_gen) before it allocates; the contents are then gone.
+void* SyncedMemory::Scratch::grow(size_t want) {
+  if (want > bytes) {
+    if (ptr) {
+      HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
+      HIP_CALL(hipFree(ptr));
+      Caffe::scratch_gen().fetch_add(1);
+    }
+    ptr = nullptr;
+    HIP_CALL(hipMalloc(&ptr, want));
+    bytes = want;
+    valid = false;
+  }
+  return ptr;
+}
+
 SyncedMemory::~SyncedMemory() {
   if (own_cpu_ && cpu_ptr_) std::free(cpu_ptr_);
   if (own_gpu_ && gpu_ptr_) (void)hipFree(gpu_ptr_);
-  if (oct_ptr_) (void)hipFree(oct_ptr_);
-  if (wp_ptr_) (void)hipFree(wp_ptr_);
-  if (wf_ptr_) (void)hipFree(wf_ptr_);
-  if (rw_ptr_) (void)hipFree(rw_ptr_);
 }
 
-void* SyncedMemory::rows(size_t bytes) {
-  if (bytes > rw_bytes_) {
-    if (rw_ptr_) {
-      HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
-      HIP_CALL(hipFree(rw_ptr_));
-      Caffe::scratch_gen().fetch_add(1);
-    }
-    rw_ptr_ = nullptr;
-    HIP_CALL(hipMalloc(&rw_ptr_, bytes));
-    rw_bytes_ = bytes;
-    rw_valid_ = false;
-  }
-  return rw_ptr_;
-}
+void* SyncedMemory::rows(size_t bytes) { return rw_.grow(bytes); }
+void* SyncedMemory::wflip(size_t bytes) { return wf_.grow(bytes); }
+void* SyncedMemory::wpack(size_t bytes) { return wp_.grow(bytes); }
+void* SyncedMemory::octets(size_t bytes) { return oct_.grow(bytes); }
 
-void* SyncedMemory::wflip(size_t bytes) {
-  if (bytes > wf_bytes_) {
-    if (wf_ptr_) {
-      HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
-      HIP_CALL(hipFree(wf_ptr_));
-      Caffe::scratch_gen().fetch_add(1);
-    }
-    wf_ptr_ = nullptr;
-    HIP_CALL(hipMalloc(&wf_ptr_, bytes));
-    wf_bytes_ = bytes;
-    wf_valid_ = false;
-  }
-  return wf_ptr_;
-}
-
-void* SyncedMemory::wpack(size_t bytes) {
-  if (bytes > wp_bytes_) {
-    if (wp_ptr_) {
-      HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
-      HIP_CALL(hipFree(wp_ptr_));
-      Caffe::scratch_gen().fetch_add(1);
-    }
-    wp_ptr_ = nullptr;
-    HIP_CALL(hipMalloc(&wp_ptr_, bytes));
-    wp_bytes_ = bytes;
-    wp_valid_ = false;
-  }
-  return wp_ptr_;
-}
-
-void* SyncedMemory::octets(size_t bytes) {
-  if (bytes > oct_bytes_) {
-    if (oct_ptr_) {
-      HIP_CALL(hipStreamSynchronize(Caffe::hip_stream()));
-      HIP_CALL(hipFree(oct_ptr_));
-      Caffe::scratch_gen().fetch_add(1);
-    }
-    oct_ptr_ = nullptr;
-    HIP_CALL(hipMalloc(&oct_ptr_, bytes));
-    oct_bytes_ = bytes;
-    oct_valid_ = false;
-  }
-  return oct_ptr_;
-}
 const void* SyncedMemory::valid_octets(const int (&shape)[4]) const {
-  if (!oct_valid_ || exposed_) return nullptr;
+  if (!oct_.valid || exposed_) return nullptr;
   for (int i = 0; i < 4; ++i)
     if (shape[i] != oct_shape_[i]) return nullptr;
-  return oct_ptr_;
+  return oct_.ptr;
 }
 void SyncedMemory::set_octets_valid(const int (&shape)[4]) {
   for (int i = 0; i < 4; ++i) oct_shape_[i] = shape[i];
-  oct_valid_ = oct_ptr_ != nullptr;
+  oct_.valid = oct_.ptr != nullptr;
 }
 
 void SyncedMemory::to_cpu() {
@@ -168,32 +128,20 @@ const void* SyncedMemory::gpu_data() {
   return gpu_ptr_;
 }
 void* SyncedMemory::mutable_cpu_data() {
-  oct_valid_ = false;
-  wp_valid_ = false;
-  wf_valid_ = false;
-  rw_valid_ = false;
-  fp32_stale = false;
+  drop_companions();
   to_cpu();
   head_ = HEAD_AT_CPU;
   return cpu_ptr_;
 }
 void* SyncedMemory::mutable_gpu_data() {
-  oct_valid_ = false;
-  wp_valid_ = false;
-  wf_valid_ = false;
-  rw_valid_ = false;
-  fp32_stale = false;
+  drop_companions();
   to_gpu();
   head_ = HEAD_AT_GPU;
   return gpu_ptr_;
 }
 void SyncedMemory::set_cpu_data(void* data) {
   CAFFE_CHECK(data, "set_cpu_data(NULL)");
-  oct_valid_ = false;
-  wp_valid_ = false;
-  wf_valid_ = false;
-  rw_valid_ = false;
-  fp32_stale = false;
+  drop_companions();
   if (own_cpu_ && cpu_ptr_) std::free(cpu_ptr_);
   cpu_ptr_ = data;
   own_cpu_ = false;
@@ -201,11 +149,7 @@ void SyncedMemory::set_cpu_data(void* data) {
 }
 void SyncedMemory::set_gpu_data(void* data) {
   CAFFE_CHECK(data, "set_gpu_data(NULL)");
-  oct_valid_ = false;
-  wp_valid_ = false;
-  wf_valid_ = false;
-  rw_valid_ = false;
-  fp32_stale = false;
+  drop_companions();
   if (own_gpu_ && gpu_ptr_) (void)hipFree(gpu_ptr_);
   gpu_ptr_ = data;
   own_gpu_ = false;

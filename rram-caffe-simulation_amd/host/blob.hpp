@@ -51,7 +51,7 @@ class SyncedMemory {
   // pre-split form of these weights, valid for one key (the layer's shape and
   // engine) until the next mutable_* / set_* access, like the octet companion.
   void* wpack(size_t bytes);  // the buffer, grown to `bytes`
-  bool wpack_valid(uint64_t key) const { return wp_valid_ && !exposed_ && wp_key_ == key; }
+  bool wpack_valid(uint64_t key) const { return wp_.valid && !exposed_ && wp_key_ == key; }
   // the C-ABI handed this memory's device pointer to a caller, who may write
   // through it at any time without a mutable access: no pack or octet
   // companion is trusted after
@@ -59,9 +59,9 @@ class SyncedMemory {
   bool exposed() const { return exposed_; }
   void set_wpack_valid(uint64_t key) {
     wp_key_ = key;
-    wp_valid_ = wp_ptr_ != nullptr;
+    wp_.valid = wp_.ptr != nullptr;
   }
-  void drop_wpack() { wp_valid_ = false; }
+  void drop_wpack() { wp_.valid = false; }
 
   // Flipped-kernel companion (rram_update_seg.w_flip): these convolution
   // weights transposed per group and rotated 180 degrees, written by the
@@ -69,12 +69,12 @@ class SyncedMemory {
   // gradient (rram_conv2d_bwd_ex).  Valid for the Solver::Step call that
   // wrote it (Caffe::step_epoch) until the next mutable_* / set_* access.
   void* wflip(size_t bytes);  // the buffer, grown to `bytes`
-  bool wflip_valid(uint64_t epoch) const { return wf_valid_ && epoch != 0 && wf_epoch_ == epoch; }
+  bool wflip_valid(uint64_t epoch) const { return wf_.valid && epoch != 0 && wf_epoch_ == epoch; }
   void set_wflip_valid(uint64_t epoch) {
     wf_epoch_ = epoch;
-    wf_valid_ = wf_ptr_ != nullptr && epoch != 0;
+    wf_.valid = wf_.ptr != nullptr && epoch != 0;
   }
-  void drop_wflip() { wf_valid_ = false; }
+  void drop_wflip() { wf_.valid = false; }
 
   // Packed-rows companion (rram_ip_fwd_rows): an InnerProduct input in the
   // bf16x6 engine's packed-row form, written by the producing InnerProduct's
@@ -82,10 +82,10 @@ class SyncedMemory {
   // until the next mutable_* / set_* access, like the octet companion.
   // wants_rows: the key a consumer asked for at Reshape (0: none).
   void* rows(size_t bytes);  // the buffer, grown to `bytes`
-  const void* valid_rows(uint64_t key) const { return rw_valid_ && !exposed_ && rw_key_ == key ? rw_ptr_ : nullptr; }
+  const void* valid_rows(uint64_t key) const { return rw_.valid && !exposed_ && rw_key_ == key ? rw_.ptr : nullptr; }
   void set_rows_valid(uint64_t key) {
     rw_key_ = key;
-    rw_valid_ = rw_ptr_ != nullptr;
+    rw_.valid = rw_.ptr != nullptr;
   }
   uint64_t wants_rows = 0;
   size_t wants_rows_bytes = 0;
@@ -98,21 +98,28 @@ class SyncedMemory {
   size_t size_;
   SyncedHead head_ = UNINITIALIZED;
   bool own_cpu_ = false, own_gpu_ = false;
-  void* oct_ptr_ = nullptr;
-  size_t oct_bytes_ = 0;
-  bool oct_valid_ = false;
+  // a grow-only device buffer owned by this memory (the four companions)
+  struct Scratch {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    bool valid = false;  // the contents match the data (cleared on growth)
+    ~Scratch() {
+      if (ptr) (void)hipFree(ptr);
+    }
+    void* grow(size_t want);  // at least `want` bytes; see blob.cpp
+  };
+  // every mutable_* / set_* access: no companion matches the data any more
+  void drop_companions() {
+    oct_.valid = wp_.valid = wf_.valid = rw_.valid = false;
+    fp32_stale = false;
+  }
+  Scratch oct_;
   int oct_shape_[4] = {0, 0, 0, 0};
-  void* wp_ptr_ = nullptr;
-  size_t wp_bytes_ = 0;
-  bool wp_valid_ = false;
+  Scratch wp_;
   uint64_t wp_key_ = 0;
-  void* rw_ptr_ = nullptr;
-  size_t rw_bytes_ = 0;
-  bool rw_valid_ = false;
+  Scratch rw_;
   uint64_t rw_key_ = 0;
-  void* wf_ptr_ = nullptr;
-  size_t wf_bytes_ = 0;
-  bool wf_valid_ = false;
+  Scratch wf_;
   uint64_t wf_epoch_ = 0;
   bool exposed_ = false;
 };

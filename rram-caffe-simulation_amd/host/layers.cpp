@@ -394,10 +394,7 @@ void InnerProductLayer<Dtype>::Reshape(const std::vector<Blob<Dtype>*>& bottom,
   const size_t rb = (this->phase_ == TEST && !transpose_ && groups_ == 1)
                         ? rram_ip_rows_pack_bytes(M_, N_, K_, ws_request(), &bmc)
                         : 0;
-#ifndef RRAM_IP_ROWS  // A/B builds: 0 = every InnerProduct packs its own input
-#define RRAM_IP_ROWS 1
-#endif
-  if (RRAM_IP_ROWS && rb > 0 && bmc > 0 && bmc < 4096) {
+  if (rb > 0 && bmc > 0 && bmc < 4096) {
     in_rows_key_ = (static_cast<uint64_t>(M_) << 40) | (static_cast<uint64_t>(K_) << 12) | static_cast<uint64_t>(bmc);
     bottom[0]->data()->wants_rows = in_rows_key_;
     bottom[0]->data()->wants_rows_bytes = rb;

@@ -7,16 +7,13 @@
 #include <set>
 #include <string>
 
-// Compile-time knobs of the injection overlap (see the constructor).
+// Constants of the injection overlap (see the constructor;
+// profiles/r05_ab_mc_overlap.txt).
 // the injection is released after this many convolutions (0: with the prefix)
-#ifndef RRAM_MC_RELEASE_AFTER_CONV
-#define RRAM_MC_RELEASE_AFTER_CONV 2
-#endif
+constexpr int kReleaseAfterConv = 2;
 // overlapped, the injection gets a 256-block grid (it shares the CUs);
 // serial, the default 2048
-#ifndef RRAM_MC_OVERLAP_GRID
-#define RRAM_MC_OVERLAP_GRID 256
-#endif
+constexpr int kOverlapGrid = 256;
 
 namespace caffe {
 
@@ -66,8 +63,8 @@ MonteCarlo<Dtype>::MonteCarlo(std::shared_ptr<Net<Dtype>> net, const std::vector
     overlap_ = e && atoi(e) == 1 && first_fault_layer_ > 0;
   }
   release_after_ = -1;  // no such convolution: the injection starts with the prefix
-  for (int i = 0, n = 0; RRAM_MC_RELEASE_AFTER_CONV && i < first_fault_layer_ - 1; ++i)
-    if (std::string(net_->layers()[i]->type()) == "Convolution" && ++n == RRAM_MC_RELEASE_AFTER_CONV) {
+  for (int i = 0, n = 0; kReleaseAfterConv && i < first_fault_layer_ - 1; ++i)
+    if (std::string(net_->layers()[i]->type()) == "Convolution" && ++n == kReleaseAfterConv) {
       release_after_ = i;
       break;
     }
@@ -471,7 +468,7 @@ void MonteCarlo<Dtype>::Run(uint32_t map_begin, uint32_t map_count) {
   const size_t no = outs_.size();
   const auto& layers = net_->layers();
   const int L = static_cast<int>(layers.size());
-  const int prev_grid = rram_set_inject_grid(overlap_ && !reuse_prefix_ ? RRAM_MC_OVERLAP_GRID : 0);
+  const int prev_grid = rram_set_inject_grid(overlap_ && !reuse_prefix_ ? kOverlapGrid : 0);
   // the statistics folded into the layers that store each scalar output
   // (Layer::set_top_accumulator): no rram_mc_accumulate launch per map when
   // every output's producer takes it (all or none)

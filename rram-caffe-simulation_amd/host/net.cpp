@@ -382,10 +382,7 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
   // forward checks: engine and plan as they stand); the fp32 top is then
   // materialised only on demand (materialize_blob; the C-ABI does for every
   // blob it hands out), like a folded LRN's top
-#ifndef RRAM_POOL_Y_FOLD  // A/B builds: 0 = the pool always writes its fp32 top
-#define RRAM_POOL_Y_FOLD 1
-#endif
-  if (RRAM_POOL_Y_FOLD && fuse_lrn_pool && phase == TEST) {
+  if (fuse_lrn_pool && phase == TEST) {
     const int L = static_cast<int>(layers_.size());
     for (const LrnFold& f : lrn_folds_) {
       if (top_id_vecs_[f.pool].size() != 1) continue;
@@ -410,10 +407,7 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
   // in-place ReLU aside) is written as the companion alone whenever the
   // producer's epilogue writes it and the reader takes it (each forward
   // checks); AlexNet conv3 -> conv4 and conv4 -> conv5
-#ifndef RRAM_CONV_Y_FOLD  // A/B builds: 0 = every convolution writes its fp32 top
-#define RRAM_CONV_Y_FOLD 1
-#endif
-  if (RRAM_CONV_Y_FOLD && fuse_conv_y && phase == TEST) {
+  if (fuse_conv_y && phase == TEST) {
     const int L = static_cast<int>(layers_.size());
     for (int l = 0; l < L; ++l) {
       if (dynamic_cast<ConvolutionLayer<Dtype>*>(layers_[l].get()) == nullptr || top_id_vecs_[l].size() != 1)
@@ -594,19 +588,12 @@ void Net<Dtype>::Update() {
 
 template <typename Dtype>
 void Net<Dtype>::ClearParamDiffs(unsigned long long* also, int64_t n_also) {
-#ifndef RRAM_ZERO_PAIR  // A/B builds: 0 = the round-5 clears (a memset here, the counters' in FusedTail)
-#define RRAM_ZERO_PAIR 1
-#endif
-  if (flat_diff_ && RRAM_ZERO_PAIR) {  // every learnable diff lives in one buffer: one launch, with the caller's counters
+  if (flat_diff_) {  // every learnable diff lives in one buffer: one launch, with the caller's counters
     RRAM_CALL(rram_zero_pair(flat_diff_, flat_param_count(), also, also ? n_also : 0, Caffe::stream()));
     return;
   }
-  if (flat_diff_) {
-    HIP_CALL(hipMemsetAsync(flat_diff_, 0, flat_param_count() * sizeof(Dtype), Caffe::hip_stream()));
-  } else {
-    for (auto* p : learnable_params_)
-      HIP_CALL(hipMemsetAsync(p->mutable_gpu_diff(), 0, p->count() * sizeof(Dtype), Caffe::hip_stream()));
-  }
+  for (auto* p : learnable_params_)
+    HIP_CALL(hipMemsetAsync(p->mutable_gpu_diff(), 0, p->count() * sizeof(Dtype), Caffe::hip_stream()));
   if (also && n_also > 0)
     HIP_CALL(hipMemsetAsync(also, 0, n_also * sizeof(unsigned long long), Caffe::hip_stream()));
 }
