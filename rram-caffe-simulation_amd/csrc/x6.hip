@@ -2390,6 +2390,10 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_rows_x6(const float* __re
 
 float* pack_buffer(size_t floats, hipStream_t s);  // gemm.hip
 
+// count elements of elem_bytes each end below 2 GB: the kernels' 32-bit byte
+// offsets (buffer ranges, epilogues).  elem_bytes = 1: a count that fits an int.
+constexpr bool fits_i32(int64_t count, int elem_bytes = 1) { return count * elem_bytes < (1ll << 31); }
+
 // most patch rows (output rows + KH - 1 halo per image segment) any BN-position
 // tile of an OH x OW output needs; -1 when a tile spans more than maxseg images
 int patch_rows(int N, int HW, int OW, int OH, int KH, int BN, int maxseg) {
@@ -2409,70 +2413,106 @@ int patch_rows(int N, int HW, int OW, int OH, int KH, int BN, int maxseg) {
   return rmax;
 }
 
-template <int KH, int CPH, int MI, int PD>
-int launch_patch_x6(Params P, const uint16_t* wpack, int PW, int CS, int gz, hipStream_t s) {
-  P.tiles_m = (P.M + 32 * MI - 1) / (32 * MI);
-  P.tiles_n = (P.N + x6::BN - 1) / x6::BN;
-  P.tiles_z = gz;
-  const int64_t nwg = (int64_t)P.tiles_m * P.tiles_n * gz;
-  RRAM_REQUIRE(nwg < (1ll << 31), "conv: grid too large");
-  hipLaunchKernelGGL((k_conv_patch_x6<KH, KH, CPH, MI, PD>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, P, wpack,
-                     PW, CS);
-  return launch_status("conv patch x6");
+// ---- what the five launchers share ----
+// The Params every launcher starts from: one group's GEMM shape (M rows, K =
+// its channels x taps) and the NCHW epilogue with the output's image stride
+// (wk.y_img, else dense).  The 1x1 kernels take it as it is, the others add
+// the window (conv_window); the rest (P.b, grp_*, tiles) is each launcher's own.
+Params conv_params(const rram_conv_desc* d, const WPack& wk, float* y, const float* bias, int relu) {
+  const int Cg = d->channels / d->group, HW = d->out_h * d->out_w;
+  Params P{};
+  P.M = d->num_output / d->group;
+  P.N = d->num * HW;
+  P.K = Cg * d->kernel_h * d->kernel_w;
+  P.split = 1;
+  P.cv.C = Cg;
+  P.cv.howo = make_fastdiv(HW);
+  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
+  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)d->num_output * HW;
+  P.e.hw = make_fastdiv(HW);
+  return P;
+}
+void conv_window(const rram_conv_desc* d, ConvGeom& cv) {
+  cv.H = d->height;
+  cv.W = d->width;
+  cv.KH = d->kernel_h;
+  cv.KW = d->kernel_w;
+  cv.ph = d->pad_h;
+  cv.pw = d->pad_w;
+  cv.sh = d->stride_h;
+  cv.sw = d->stride_w;
+  cv.dh = d->dilation_h;
+  cv.dw = d->dilation_w;
+  cv.Ho = d->out_h;
+  cv.Wo = d->out_w;
+  cv.wo_div = make_fastdiv(d->out_w);
+}
+// the kernels that read x itself (fp32 NCHW): a buffer over the whole input
+void conv_input_view(const rram_conv_desc* d, const float* x, Params& P) {
+  P.b = make_view(x, 0, P.N, P.K);
+  P.cv.chw = (int64_t)d->channels * d->height * d->width;
+  P.cv.in_bytes = static_cast<int>((int64_t)d->num * P.cv.chw * 4);
 }
 
+// The weight-pack protocol of every family.  A pack-bytes query (wk.query) is
+// answered here: 1, nothing launched.  Else the pack lies in the caller's
+// buffer (wk.p) or in the stream's scratch buffer, there behind `lead` bytes
+// that the launcher wants from the same allocation (the channel-octet
+// kernels' packed input; pack_lead fills them first), and pack_w launches the
+// family's pack kernel unless the caller's buffer already holds the pack
+// (wk.valid).  0: *wbuf is ready; < 0: error.
+template <class PackW, class PackLead>
+int conv_weight_pack(const WPack& wk, int64_t wbytes, hipStream_t s, const char* what, PackW pack_w, char** wbuf,
+                     int64_t lead, PackLead pack_lead) {
+  if (wk.query) {
+    *wk.query = static_cast<size_t>(wbytes);
+    return 1;
+  }
+  const int64_t scratch = lead + (wk.p ? 0 : wbytes);
+  char* buf = scratch > 0 ? reinterpret_cast<char*>(pack_buffer(static_cast<size_t>((scratch + 3) / 4), s)) : nullptr;
+  RRAM_REQUIRE(scratch == 0 || buf != nullptr, "conv: packed-operand buffer allocation failed");
+  *wbuf = wk.p ? static_cast<char*>(wk.p) : buf + lead;
+  int rc = pack_lead(buf);
+  if (rc == 0 && !wk.valid) {
+    pack_w(*wbuf);
+    rc = launch_status(what);
+  }
+  return rc;
+}
+template <class PackW>
+int conv_weight_pack(const WPack& wk, int64_t wbytes, hipStream_t s, const char* what, PackW pack_w, char** wbuf) {
+  return conv_weight_pack(wk, wbytes, s, what, pack_w, wbuf, 0, [](char*) { return 0; });
+}
+
+// Each launcher below takes the plan conv_x6_select made for d and returns 1
+// when it ran (or answered wk.query), 0 when not covered, < 0 on error.
 
 // ---- k_conv1_ring_x6 (AlexNet conv1: 3 x 227 x 227, 96 x 11 x 11, stride 4) ----
 bool conv1_ring_ok(const rram_conv_desc* d) {
   return d->group == 1 && d->channels == 3 && d->kernel_h == 11 && d->kernel_w == 11 && d->stride_h == 4 &&
          d->stride_w == 4 && d->pad_h == 0 && d->pad_w == 0 && d->dilation_h == 1 && d->dilation_w == 1 &&
          d->width == 227 && d->height >= 11 && d->num_output == c1x6::BM && d->num > 0 &&
-         (int64_t)d->num * 3 * d->height * d->width * 4 < (1ll << 31) &&
-         (int64_t)d->num * d->num_output * d->out_h * d->out_w * 4 < (1ll << 31);
+         fits_i32((int64_t)d->num * 3 * d->height * d->width, 4) &&
+         fits_i32((int64_t)d->num * d->num_output * d->out_h * d->out_w, 4);
 }
 
 int conv_wide_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,
                      hipStream_t s, const WPack& wk) {
-  if (!conv1_ring_ok(d)) return 0;
-  if ((reinterpret_cast<uintptr_t>(w) & 3u) != 0) return 0;
   const int HW = d->out_h * d->out_w;
-  Params P{};
-  P.M = d->num_output;
-  P.N = d->num * HW;
-  P.K = 3 * 121;
-  P.split = 1;
-  P.b = make_view(x, 0, P.N, P.K);
-  ConvGeom& cv = P.cv;
-  cv.C = 3;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = cv.KW = 11;
-  cv.sh = cv.sw = 4;
-  cv.dh = cv.dw = 1;
-  cv.Ho = d->out_h;
-  cv.Wo = d->out_w;
-  cv.howo = make_fastdiv(HW);
-  cv.wo_div = make_fastdiv(d->out_w);
-  cv.chw = (int64_t)3 * d->height * d->width;
-  cv.in_bytes = static_cast<int>((int64_t)d->num * cv.chw * 4);
-  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
-  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)d->num_output * HW;
-  P.e.hw = make_fastdiv(HW);
+  Params P = conv_params(d, wk, y, bias, relu);
+  conv_window(d, P.cv);
+  conv_input_view(d, x, P);
   // the epilogue's 32-bit output offsets (image stride included)
-  if ((int64_t)d->num * P.e.cimg * 4 >= (1ll << 31)) return 0;
+  if (!fits_i32((int64_t)d->num * P.e.cimg, 4)) return 0;
   const int units = c1x6::G * 3 * 64;  // 3 KB fragments
-  const size_t wbytes = static_cast<size_t>(units) * 48;
-  if (wk.query) {
-    *wk.query = wbytes;
-    return 1;
-  }
-  char* wp = static_cast<char*>(wk.p ? wk.p : pack_buffer((wbytes + 3) / 4, s));
-  RRAM_REQUIRE(wp != nullptr, "conv: packed-weight buffer allocation failed");
-  if (!wk.valid) {
-    hipLaunchKernelGGL(k_conv1_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w, wp, d->num_output, units);
-    const int rc = launch_status("conv1 weight pack x6");
-    if (rc) return rc;
-  }
+  char* wp = nullptr;
+  if (const int rc = conv_weight_pack(
+          wk, (int64_t)units * 48, s, "conv1 weight pack x6",
+          [&](char* p) {
+            hipLaunchKernelGGL(k_conv1_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w, p, d->num_output, units);
+          },
+          &wp))
+    return rc;
   // (a non-persistent form at two workgroups of six waves per CU, 96 x 128
   // tiles, two channel slots: 0.462 vs 0.326 ms, profiles/r05_ab_c1_pair.txt)
   const int tpi = (HW + c1x6::BN - 1) / c1x6::BN;
@@ -2498,57 +2538,31 @@ bool conv_s2_ok(const rram_conv_desc* d) {
          d->pad_h <= 3 && d->pad_w >= 0 && d->pad_w <= 3 && d->num_output >= 1 && d->num_output <= k::BM &&
          d->num > 0 && d->out_w >= 85 && d->out_h >= 1 && k::S * (d->out_w - 1) + k::KC <= k::ROWE &&
          (d->out_w + T::BN - 2) / d->out_w <= T::OR - 1 &&
-         (int64_t)d->num * k::C * d->height * d->width * 4 < (1ll << 31) &&
-         (int64_t)d->num * d->num_output * d->out_h * d->out_w * 4 < (1ll << 31);
+         fits_i32((int64_t)d->num * k::C * d->height * d->width, 4) &&
+         fits_i32((int64_t)d->num * d->num_output * d->out_h * d->out_w, 4);
 }
 
 int conv_s2_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,
                    hipStream_t s, const WPack& wk) {
-  if (!conv_s2_ok(d)) return 0;
-  if ((reinterpret_cast<uintptr_t>(w) & 3u) != 0) return 0;
   const int HW = d->out_h * d->out_w;
-  Params P{};
-  P.M = d->num_output;
-  P.N = d->num * HW;
-  P.K = c7x6::R * c7x6::KS;
-  P.split = 1;
-  P.b = make_view(x, 0, P.N, P.K);
-  ConvGeom& cv = P.cv;
-  cv.C = c7x6::C;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = cv.KW = c7x6::KS;
-  cv.ph = d->pad_h;
-  cv.pw = d->pad_w;
-  cv.sh = cv.sw = c7x6::S;
-  cv.dh = cv.dw = 1;
-  cv.Ho = d->out_h;
-  cv.Wo = d->out_w;
-  cv.howo = make_fastdiv(HW);
-  cv.wo_div = make_fastdiv(d->out_w);
-  cv.chw = (int64_t)c7x6::C * d->height * d->width;
-  cv.in_bytes = static_cast<int>((int64_t)d->num * cv.chw * 4);
-  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
-  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)d->num_output * HW;
-  P.e.hw = make_fastdiv(HW);
+  Params P = conv_params(d, wk, y, bias, relu);
+  conv_window(d, P.cv);
+  conv_input_view(d, x, P);
   // the epilogue's 32-bit output offsets (image stride included)
-  if ((int64_t)d->num * P.e.cimg * 4 >= (1ll << 31)) return 0;
+  if (!fits_i32((int64_t)d->num * P.e.cimg, 4)) return 0;
   const int units = c7x6::G * c7x6::MI * 64;  // 3 KB fragments
-  const size_t wbytes = static_cast<size_t>(units) * 48;
-  if (wk.query) {
-    *wk.query = wbytes;
-    return 1;
-  }
-  char* wp = static_cast<char*>(wk.p ? wk.p : pack_buffer((wbytes + 3) / 4, s));
-  RRAM_REQUIRE(wp != nullptr, "conv: packed-weight buffer allocation failed");
-  if (!wk.valid) {
-    hipLaunchKernelGGL(k_conv_s2_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w, wp, d->num_output, units);
-    const int rc = launch_status("conv s2 weight pack x6");
-    if (rc) return rc;
-  }
+  char* wp = nullptr;
+  if (const int rc = conv_weight_pack(
+          wk, (int64_t)units * 48, s, "conv s2 weight pack x6",
+          [&](char* p) {
+            hipLaunchKernelGGL(k_conv_s2_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w, p, d->num_output,
+                               units);
+          },
+          &wp))
+    return rc;
   const int tpi = (HW + c7x6::Tile<kS2Nbw>::BN - 1) / c7x6::Tile<kS2Nbw>::BN;
   const int64_t tiles = (int64_t)d->num * tpi;
-  RRAM_REQUIRE(tiles < (1ll << 31), "conv: grid too large");
+  RRAM_REQUIRE(fits_i32(tiles), "conv: grid too large");
   // (a persistent form, one workgroup per CU with the weights in registers:
   // 0.61 vs 0.43 ms in the GoogLeNet map, profiles/r06_ab_conv_s2_persistent.txt)
   hipLaunchKernelGGL(k_conv_s2_x6<kS2Nbw>, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, s, P,
@@ -2557,7 +2571,8 @@ int conv_s2_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, cons
   return rc ? rc : 1;
 }
 
-// engine of the stride-1 3x3 / 5x5 convolutions (rram_set_f32_engine)
+// engine of the stride-1 3x3 / 5x5 convolutions (rram_set_f32_engine);
+// RRAM_X6 = 0 starts on the fp32-MFMA kernels
 std::atomic<int>& f32_engine() {
   static std::atomic<int> eng{[] {
     const char* e = getenv("RRAM_X6");
@@ -2566,17 +2581,31 @@ std::atomic<int>& f32_engine() {
   return eng;
 }
 
-// k_conv_patch_x6 (fp32 products on the bf16 matrix cores, see the kernel):
+// ---- k_conv_patch_x6 (fp32 products on the bf16 matrix cores, see the kernel) ----
 // stride-1 undilated 3x3 / 5x5 convolutions with >= 128 positions per output
-// plane and <= 1/8 padded rows in the 96- or 128-row M tiles.  Returns 1 when it ran,
-// 0 when not covered, < 0 on error.  RRAM_X6 = 0 keeps the fp32-MFMA kernels.
-// shape plan of the x6 convolution (false: not covered)
+// plane and <= 1/8 padded rows in the 96- or 128-row M tiles
 struct ConvPlan {
   int CPH, MI, mt, PW, CS, PD;
 };
 // instantiated (KH, CPH, PD) combinations of k_conv_patch_x6, each at MI = 3 and 4
 #define RRAM_PATCH_LIST(X) \
   X(5, 1, 4) X(5, 1, 8) X(5, 1, 12) X(3, 4, 8) X(3, 4, 12) X(3, 4, 16) X(3, 2, 4) X(3, 2, 8) X(3, 2, 16)
+struct PatchForm {
+  int KH, CPH, PD;
+};
+constexpr PatchForm kPatchForms[] = {
+#define RRAM_X(kh, cph, pd) {kh, cph, pd},
+    RRAM_PATCH_LIST(RRAM_X)
+#undef RRAM_X
+};
+// the least built patch depth >= need pieces for (KH, CPH); 0: none
+int patch_pd(int KH, int CPH, int need) {
+  int pd = 0;
+  for (const PatchForm& f : kPatchForms)
+    if (f.KH == KH && f.CPH == CPH && f.PD >= need && (pd == 0 || f.PD < pd)) pd = f.PD;
+  return pd;
+}
+bool patch_built(int KH, int CPH, int PD) { return PD > 0 && patch_pd(KH, CPH, PD) == PD; }
 bool conv_x6_plan(const rram_conv_desc* d, ConvPlan& pl) {
   const int KH = d->kernel_h, KW = d->kernel_w;
   if (d->stride_h != 1 || d->stride_w != 1 || d->dilation_h != 1 || d->dilation_w != 1) return false;
@@ -2585,8 +2614,8 @@ bool conv_x6_plan(const rram_conv_desc* d, ConvPlan& pl) {
   const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h;
   pl.CPH = KH == 5 ? 1 : (Cg % 8 == 0 ? 4 : 2);
   if (HW < 128 || Cg == 0 || Cg % (2 * pl.CPH) != 0) return false;
-  if ((int64_t)d->num * d->channels * d->height * d->width * 4 >= (1ll << 31)) return false;  // 32-bit offsets
-  if ((int64_t)d->num * d->num_output * HW * 4 >= (1ll << 31)) return false;                   // (output too)
+  if (!fits_i32((int64_t)d->num * d->channels * d->height * d->width, 4)) return false;  // 32-bit offsets
+  if (!fits_i32((int64_t)d->num * d->num_output * HW, 4)) return false;                   // (output too)
   // M tile 128 or 96 rows, whichever pads less (<= 1/8 padded rows)
   const int t128 = (M + 127) / 128 * 128, t96 = (M + 95) / 96 * 96;
   pl.MI = (t96 - M) < (t128 - M) ? 3 : 4;
@@ -2599,21 +2628,65 @@ bool conv_x6_plan(const rram_conv_desc* d, ConvPlan& pl) {
   // halves read disjoint bank halves
   pl.CS = rmax * pl.PW;
   while ((pl.CPH * pl.CS) % 64 != 32) ++pl.CS;
-  const int need = (2 * pl.CPH * pl.CS + 255) / 256;  // 256-float patch pieces
-  static const int pd5[] = {4, 8, 12}, pd3q[] = {8, 12, 16}, pd3h[] = {4, 8, 16};
-  const int* pds = KH == 5 ? pd5 : pl.CPH == 4 ? pd3q : pd3h;
-  pl.PD = 0;
-  for (int i = 2; i >= 0; --i)
-    if (pds[i] >= need) pl.PD = pds[i];
+  pl.PD = patch_pd(KH, pl.CPH, (2 * pl.CPH * pl.CS + 255) / 256);  // 256-float patch pieces
   if (pl.PD == 0) return false;
   const int64_t total = (int64_t)G * (pl.mt / (32 * pl.MI)) * (Cg / (2 * pl.CPH)) * 32 * pl.MI *
                         (((KH * KW * pl.CPH + 7) / 8 * 96 + 16) / 2);
-  return total * 2 < (1ll << 31);
+  return fits_i32(total, 2);
+}
+
+template <int KH, int CPH, int MI, int PD>
+int launch_patch_x6(Params P, const uint16_t* wpack, int PW, int CS, int gz, hipStream_t s) {
+  P.tiles_m = (P.M + 32 * MI - 1) / (32 * MI);
+  P.tiles_n = (P.N + x6::BN - 1) / x6::BN;
+  P.tiles_z = gz;
+  const int64_t nwg = (int64_t)P.tiles_m * P.tiles_n * gz;
+  RRAM_REQUIRE(fits_i32(nwg), "conv: grid too large");
+  hipLaunchKernelGGL((k_conv_patch_x6<KH, KH, CPH, MI, PD>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, P, wpack,
+                     PW, CS);
+  return launch_status("conv patch x6");
+}
+
+int conv_patch_x6_fwd(const rram_conv_desc* d, const ConvPlan& pl, const float* x, const float* w, const float* bias,
+                      float* y, int relu, hipStream_t s, const WPack& wk) {
+  const int KH = d->kernel_h, T = KH * d->kernel_w;
+  const int G = d->group, Cg = d->channels / G, M = d->num_output / G;
+  const int CPH = pl.CPH, MI = pl.MI, PW = pl.PW, CS = pl.CS, PD = pl.PD;
+  Params P = conv_params(d, wk, y, bias, relu);
+  conv_window(d, P.cv);
+  conv_input_view(d, x, P);
+  P.grp_b = (int64_t)Cg * d->height * d->width;
+  P.grp_c = (int64_t)M * d->out_h * d->out_w;
+  P.grp_bias = M;
+  const int S = CPH * T, G8 = (S + 7) / 8, RLH = (G8 * 96 + 16) / 2;
+  const int BMc = 32 * MI, tiles_m = pl.mt / BMc, ktiles = Cg / (2 * CPH);
+  const int64_t total = (int64_t)G * tiles_m * ktiles * BMc * RLH;
+  char* wbuf = nullptr;
+  if (const int rc = conv_weight_pack(
+          wk, total * 2, s, "conv weight pack x6",
+          [&](char* p) {
+            const int units = G * tiles_m * ktiles * BMc * G8 * 2;
+            hipLaunchKernelGGL(k_conv_patch_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w, p, G, M, Cg, T,
+                               CPH, G8, 2 * RLH, BMc, tiles_m, ktiles, units);
+          },
+          &wbuf))
+    return rc;
+  const uint16_t* wp = reinterpret_cast<const uint16_t*>(wbuf);
+  int rc = 0;
+#define RRAM_P(KH_, CPH_, PD_)                                                                           \
+  if (KH == KH_ && CPH == CPH_ && PD == PD_)                                                             \
+    rc = MI == 3 ? launch_patch_x6<KH_, CPH_, 3, PD_>(P, wp, PW, CS, G, s)                               \
+                 : launch_patch_x6<KH_, CPH_, 4, PD_>(P, wp, PW, CS, G, s);                              \
+  else
+  RRAM_PATCH_LIST(RRAM_P)
+  RRAM_REQUIRE(false, "conv: the plan names a patch kernel that is not built");
+#undef RRAM_P
+  return rc ? rc : 1;
 }
 
 // x [num][C][HWi] fp32 -> its octet companion (C % 8 == 0)
 int pack_octets(const float* x, void* oct, int num, int C, int HWi, hipStream_t s) {
-  RRAM_REQUIRE(C % 8 == 0 && (int64_t)num * C * HWi * 6 < (1ll << 31), "pack_octets: C %% 8 != 0 or too large");
+  RRAM_REQUIRE(C % 8 == 0 && fits_i32((int64_t)num * C * HWi, 6), "pack_octets: C %% 8 != 0 or too large");
   const int units = num * (C / 8) * HWi;
   if (units == 0) return RRAM_OK;
   hipLaunchKernelGGL(k_pack_octets_x6, dim3(stream_blocks(units)), dim3(256), 0, s, x, static_cast<char*>(oct), C / 8,
@@ -2631,7 +2704,9 @@ struct CbPlan {
 };
 // instantiated (KH, WR, NB, PD, OCC) combinations; OCC = workgroups per CU.
 // One workgroup per CU: k_conv_cb_x6 (32x32x16); two: k_conv_cb16_x6
-// (16x16x32, RRAM_CB16_LIST below)
+// (16x16x32, RRAM_CB16_LIST below).  The planner tries a family's (WR, NB)
+// tiles in the order of their first line here, and ties go to the first.
+// (the other tiles per layer measured slower: profiles/r02_ab_cb_cfg.txt)
 #define RRAM_CB_LIST(X)                                                                              \
   X(5, 4, 8, 15, 1) X(5, 4, 4, 12, 1) X(5, 4, 4, 14, 1) X(5, 2, 4, 14, 1) X(3, 4, 8, 12, 1)          \
   X(3, 4, 8, 15, 1) X(3, 4, 4, 8, 1) X(3, 4, 4, 12, 1) X(3, 2, 4, 12, 1) X(3, 2, 4, 14, 1)
@@ -2641,117 +2716,165 @@ struct CbPlan {
 // of two rounds a third full, measured slower: 0.180-0.183 vs 0.166-0.168 ms,
 // profiles/r05_ab_conv5_n64.txt)
 #define RRAM_CB16_LIST(X) X(5, 4, 4, 8, 2) X(3, 4, 4, 8, 2) X(3, 2, 2, 8, 2)
-bool cb_instantiated(int KH, int WR, int NB, int PD, int OCC = 1) {
-#define RRAM_X(kh, wr, nb, pd, occ) \
-  if (KH == kh && WR == wr && NB == nb && PD == pd && OCC == occ) return true;
-  RRAM_CB_LIST(RRAM_X)
-  RRAM_CB16_LIST(RRAM_X)
+struct CbForm {
+  int KH, WR, NB, PD, OCC;
+};
+constexpr CbForm kCbForms[] = {
+#define RRAM_X(kh, wr, nb, pd, occ) {kh, wr, nb, pd, occ},
+    RRAM_CB_LIST(RRAM_X) RRAM_CB16_LIST(RRAM_X)
 #undef RRAM_X
-  return false;
+};
+constexpr int kCbFormCount = sizeof(kCbForms) / sizeof(kCbForms[0]);
+// the least built LDS depth >= need pieces of a (KH, WR, NB, OCC) tile; 0: none
+int cb_pd(int KH, int WR, int NB, int OCC, int need) {
+  int pd = 0;
+  for (const CbForm& f : kCbForms)
+    if (f.KH == KH && f.WR == WR && f.NB == NB && f.OCC == OCC && f.PD >= need && (pd == 0 || f.PD < pd)) pd = f.PD;
+  return pd;
 }
-// Planes of < 64 positions (GoogLeNet's 7 x 7 stage): 128 consecutive
-// positions would span 4 images (the patch holds 3 segments), so the tiles are
-// whole images -- tp = floor(128 / HW) images' positions per 128-column tile
-// at two workgroups per CU, the columns past tp computed and dropped -- when
-// the patch of those images fits the 8 LDS pieces.
-bool conv_cb_plan_whole_images(const rram_conv_desc* d, CbPlan& pl) {
-  const int KH = d->kernel_h, G = d->group, M = d->num_output / G;
-  const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h, N = d->num * HW;
-  if ((int64_t)d->num * d->channels * d->height * d->width * 6 >= (1ll << 31)) return false;  // 32-bit offsets
-  if ((int64_t)d->num * d->num_output * HW * 4 >= (1ll << 31)) return false;
-  const int PW = d->width + 2 * d->pad_w;
-  int RPC = 3 * PW;
-  while ((RPC - 3 * OW) % 16 != 0) ++RPC;
-  // 128 x 128 tiles where no row pads, else 64 x 128 (the instantiated ones)
-  static const int cfg[2][2] = {{4, 4}, {2, 2}};
-  for (const auto& c : cfg) {
-    const int WR = c[0], NB = c[1], BM = 32 * WR, BN = 32 * NB * (4 / WR);
-    if (HW > BN / 2 || !cb_instantiated(KH, WR, NB, 8, 2)) continue;
-    const int tiles_m = (M + BM - 1) / BM;
-    if (WR == 4 && tiles_m * BM != M && cb_instantiated(KH, 2, 2, 8, 2)) continue;
-    if ((tiles_m * BM - M) * 4 > tiles_m * BM) continue;
-    const int per = std::min(BN / HW, 3), tp = per * HW;  // (the patch holds 3 segments)
-    const int rmax = per * (OH + KH - 1);
-    const int octb = ((rmax * RPC + 2 * ((3 * OW * (1 - KH)) & 15)) * 16 + 255) / 256 * 256;
-    if ((2 * octb / 16 + 255) / 256 > 8) continue;
-    const int64_t tiles_n = (N + tp - 1) / tp;
-    if ((int64_t)G * tiles_m * tiles_n >= (1ll << 31)) continue;
-    pl = CbPlan{WR, NB, RPC, 8, octb, tiles_m, static_cast<int>(tiles_n), 2, 0};
-    pl.tp = tp;
-    pl.kind = CB_WHOLE;
-    return true;
+bool cb_built(int KH, int WR, int NB, int PD, int OCC) { return PD > 0 && cb_pd(KH, WR, NB, OCC, PD) == PD; }
+// f(WR, NB) for each tile built for KH at OCC workgroups per CU, once each in
+// list order, until one returns true (the result)
+template <class F>
+bool cb_tiles(int KH, int OCC, F f) {
+  for (int i = 0; i < kCbFormCount; ++i) {
+    const CbForm& a = kCbForms[i];
+    if (a.KH != KH || a.OCC != OCC) continue;
+    bool seen = false;
+    for (int j = 0; j < i; ++j)
+      seen = seen || (kCbForms[j].KH == KH && kCbForms[j].OCC == OCC && kCbForms[j].WR == a.WR && kCbForms[j].NB == a.NB);
+    if (!seen && f(a.WR, a.NB)) return true;
   }
   return false;
 }
+
+// octet plane size of a patch of rmax rows, rounded to 256 bytes: the
+// 16x16x32 form reads both planes in one ds_read_b128 lane group,
+// conflict-free only when the plane offset is a multiple of the 64 banks
+// (seg_shifts: + the two segment shifts of cbx6::seg_shift, tiles that span images)
+int octb_of(int rmax, int RPC, int OW, int KH, bool seg_shifts) {
+  return ((rmax * RPC + (seg_shifts ? 2 * ((3 * OW * (1 - KH)) & 15) : 0)) * 16 + 255) / 256 * 256;
+}
+// most patch rows of a per-image tile of BN positions: one halo each, the last
+// tile of an image short
+int perimg_rows(int HW, int BN, int OW, int KH) {
+  int rm = 0;
+  for (int t = 0; t * BN < HW; ++t) {
+    const int f = t * BN / OW, l = (std::min((t + 1) * BN, HW) - 1) / OW;
+    rm = std::max(rm, l - f + KH);
+  }
+  return rm;
+}
+
+// One candidate of the channel-octet planner: tiles of 32 WR x 32 NB (4 / WR)
+// at OCC workgroups per CU, laid on the output positions as `kind`:
+//   CB_CONTIG    consecutive positions (a tile spans up to 3 images)
+//   CB_PERIMG    per-image tiles of this shape, one halo each, the last tile
+//                of an image short
+//   CB_ROWALIGN  per-image tiles of whole output rows (tp = the rows of OW
+//                that fit BN; the columns past tp computed and dropped), whose
+//                patch has no partial rows
+//   CB_WHOLE     planes of < 64 positions: whole images, tp = up to 3 images'
+//                positions per tile (the patch holds 3 segments), the columns
+//                past tp computed and dropped
+// false: it does not fit (*deep set: only because its patch takes more LDS
+// pieces than a built form has).  cost: the makespan in rounds of 256 (512
+// half-CU) workgroups x tile area.
+bool cb_candidate(const rram_conv_desc* d, int RPC, int kind, int WR, int NB, int OCC, CbPlan& pl, int64_t& cost,
+                  bool* deep = nullptr) {
+  const int KH = d->kernel_h, G = d->group, M = d->num_output / G;
+  const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h, N = d->num * HW;
+  const int BM = 32 * WR, BN = 32 * NB * (4 / WR), tiles_m = (M + BM - 1) / BM;
+  if ((tiles_m * BM - M) * 4 > tiles_m * BM) return false;  // > 1/4 padded rows
+  int rmax = 0, tpi = 0, tp = 0;
+  int64_t tiles_n = 0;
+  switch (kind) {
+    case CB_CONTIG:
+      rmax = patch_rows(N, HW, OW, OH, KH, BN, 3);
+      if (rmax < 0) return false;
+      tiles_n = (N + BN - 1) / BN;
+      break;
+    case CB_PERIMG:
+      tpi = (HW + BN - 1) / BN;
+      rmax = perimg_rows(HW, BN, OW, KH);
+      break;
+    case CB_ROWALIGN:
+      if (OW > BN || BN % OW == 0 || HW <= BN) return false;
+      tp = BN / OW * OW;
+      tpi = (HW + tp - 1) / tp;
+      rmax = tp / OW + KH - 1;
+      break;
+    default: {  // CB_WHOLE
+      if (HW > BN / 2) return false;
+      const int per = std::min(BN / HW, 3);
+      tp = per * HW;
+      rmax = per * (OH + KH - 1);
+      tiles_n = ((int64_t)N + tp - 1) / tp;
+    }
+  }
+  if (tpi > 0) tiles_n = (int64_t)tpi * d->num;
+  const int octb = octb_of(rmax, RPC, OW, KH, kind == CB_CONTIG || kind == CB_WHOLE);
+  const int PD = cb_pd(KH, WR, NB, OCC, (2 * octb / 16 + 255) / 256);  // 1 KB pieces per wave
+  if (PD == 0) {
+    if (deep) *deep = true;
+    return false;
+  }
+  const int64_t nwg = (int64_t)G * tiles_m * tiles_n;
+  if (!fits_i32(nwg)) return false;
+  // two per CU: a 64-row tile pays about a third more per MFMA (two waves read
+  // each weight fragment for half the columns): AlexNet conv5 (128 rows per
+  // group) 0.172 ms on 128 x 128 vs 0.184 on 64 x 128, while conv4
+  // (192 rows per group: 128-row tiles pad a quarter) 0.297 on its
+  // one-per-CU 64 x 256 plan vs 0.267 on 64 x 128
+  cost = OCC == 1 ? (nwg + 255) / 256 * BM * BN : (nwg + 511) / 512 * 2 * BM * BN * (BM == 64 ? 4 : 3) / 3;
+  pl = CbPlan{WR, NB, RPC, PD, octb, tiles_m, static_cast<int>(tiles_n), OCC, tpi};
+  pl.tp = tp;
+  pl.kind = kind;
+  return true;
+}
+
 bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
   const int KH = d->kernel_h, KW = d->kernel_w;
   if (d->stride_h != 1 || d->stride_w != 1 || d->dilation_h != 1 || d->dilation_w != 1) return false;
   if (!((KH == 3 && KW == 3) || (KH == 5 && KW == 5))) return false;
   const int G = d->group, Cg = d->channels / G, M = d->num_output / G;
-  const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h, N = d->num * HW;
+  const int HW = d->out_h * d->out_w, OW = d->out_w;
   if (Cg % 16 != 0 || M == 0) return false;
-  if (HW < 64) return conv_cb_plan_whole_images(d, pl);
-  const int PW = d->width + 2 * d->pad_w;
-  // row pitch in 16-byte chunks: >= 3 PW, = 3 OW (mod 16) (bank-conflict-free reads)
-  int RPC = 3 * PW;
-  while ((RPC - 3 * OW) % 16 != 0) ++RPC;
   // packed input < 2 GB (32-bit buffer offsets), and the fp32 output (the
   // epilogues' 32-bit byte offsets)
-  if ((int64_t)d->num * d->channels * d->height * d->width * 6 >= (1ll << 31)) return false;
-  if ((int64_t)d->num * d->num_output * HW * 4 >= (1ll << 31)) return false;
-  // tile (WR, NB) with the least makespan (rounds of 256 workgroups x tile
-  // area); ties: taller tiles (weights fetched by one wave)
-  static const int cfg[3][2] = {{4, 8}, {4, 4}, {2, 4}};
-  // (the other tiles per layer measured slower: profiles/r02_ab_cb_cfg.txt)
+  if (!fits_i32((int64_t)d->num * d->channels * d->height * d->width, 6)) return false;
+  if (!fits_i32((int64_t)d->num * d->num_output * HW, 4)) return false;
+  // row pitch in 16-byte chunks: >= 3 PW, = 3 OW (mod 16) (bank-conflict-free reads)
+  int RPC = 3 * (d->width + 2 * d->pad_w);
+  while ((RPC - 3 * OW) % 16 != 0) ++RPC;
+  CbPlan c{};
+  int64_t cost = 0;
+  // Planes of < 64 positions (GoogLeNet's 7 x 7 stage): 128 consecutive
+  // positions would span 4 images (the patch holds 3 segments), so the tiles
+  // are whole images at two workgroups per CU, when the patch of those images
+  // fits the LDS pieces: 128 x 128 tiles where no row pads, else 64 x 128
+  if (HW < 64)
+    return cb_tiles(KH, 2, [&](int WR, int NB) {
+      if (WR == 4 && M % 128 != 0 && cb_built(KH, 2, 2, 8, 2)) return false;
+      return cb_candidate(d, RPC, CB_WHOLE, WR, NB, 2, pl, cost);
+    });
+  // one workgroup per CU: the tile with the least makespan; ties: taller
+  // tiles (weights fetched by one wave)
   int64_t best = -1;
-  for (const auto& c : cfg) {
-    const int WR = c[0], NB = c[1], BM = 32 * WR, BN = 32 * NB * (4 / WR);
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    if ((tiles_m * BM - M) * 4 > tiles_m * BM) continue;  // > 1/4 padded rows
-    const int rmax = patch_rows(N, HW, OW, OH, KH, BN, 3);
-    if (rmax < 0) continue;
-    // octet plane size rounded to 256 bytes: the 16x16x32 form reads both
-    // planes in one ds_read_b128 lane group, conflict-free only when the
-    // plane offset is a multiple of the 64 banks
-    // (+ the two segment shifts of cbx6::seg_shift)
-    const int octb = ((rmax * RPC + 2 * ((3 * OW * (1 - KH)) & 15)) * 16 + 255) / 256 * 256;
-    const int need = (2 * octb / 16 + 255) / 256;  // 1 KB pieces per wave
-    int PD = 0;
-    for (int p : {8, 12, 14, 15})
-      if (PD == 0 && p >= need && cb_instantiated(KH, WR, NB, p)) PD = p;
-    if (PD == 0) {
-      // the contiguous tiles' patch does not fit (tiles spanning two images
-      // carry two halos): per-image tiles of this shape, one halo each, the
-      // last tile of an image short (GoogLeNet conv2, 64 x 256 on 56 x 56:
-      // 13 tiles per image instead of 128 x 128 tiles with 1/4 padded rows)
-      const int tpi = (HW + BN - 1) / BN;
-      int rm = 0;
-      for (int t = 0; t < tpi; ++t) {
-        const int f = t * BN / OW, l = (std::min((t + 1) * BN, HW) - 1) / OW;
-        rm = std::max(rm, l - f + KH);
-      }
-      const int ob = (rm * RPC * 16 + 255) / 256 * 256;
-      const int nd = (2 * ob / 16 + 255) / 256;
-      for (int p : {8, 12, 14, 15})
-        if (PD == 0 && p >= nd && cb_instantiated(KH, WR, NB, p)) PD = p;
-      const int64_t nwg = (int64_t)G * tiles_m * tpi * d->num;
-      if (PD == 0 || nwg >= (1ll << 31)) continue;
-      const int64_t cost = (nwg + 255) / 256 * BM * BN;
-      if (best < 0 || cost < best) {
-        best = cost;
-        pl = CbPlan{WR, NB, RPC, PD, ob, tiles_m, static_cast<int>(tpi * d->num), 1, tpi};
-        pl.kind = CB_PERIMG;
-      }
-      continue;
-    }
-    const int64_t nwg = (int64_t)G * tiles_m * tiles_n;
-    if (nwg >= (1ll << 31)) continue;
-    const int64_t cost = (nwg + 255) / 256 * BM * BN;
+  cb_tiles(KH, 1, [&](int WR, int NB) {
+    // where the contiguous tiles' patch does not fit (tiles spanning two images
+    // carry two halos): per-image tiles (GoogLeNet conv2, 64 x 256 on 56 x 56:
+    // 13 tiles per image instead of 128 x 128 tiles with 1/4 padded rows)
+    bool deep = false;
+    if (!cb_candidate(d, RPC, CB_CONTIG, WR, NB, 1, c, cost, &deep) &&
+        !(deep && cb_candidate(d, RPC, CB_PERIMG, WR, NB, 1, c, cost)))
+      return false;
     if (best < 0 || cost < best) {
       best = cost;
-      pl = CbPlan{WR, NB, RPC, PD, octb, tiles_m, tiles_n, 1, 0};
+      pl = c;
     }
-  }
+    return false;
+  });
   // Two workgroups per CU (k_conv_cb16_x6: <= 256 registers and 8 LDS
   // pieces = 64 KB each): one workgroup's waits, prologue and epilogue then
   // run under the other's MFMAs.  Tiles 128 x 128 or 64 x 128, contiguous
@@ -2763,61 +2886,24 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
   if (best > 0) {
     int64_t best2 = -1, best3 = -1;  // best3: the row-aligned per-image plans
     CbPlan p2{}, p3{};
-    static const int cfg2[2][2] = {{4, 4}, {2, 2}};
-    for (const auto& c : cfg2) {
-      const int WR = c[0], NB = c[1], BM = 32 * WR, BN = 32 * NB * (4 / WR);
-      if (!cb_instantiated(KH, WR, NB, 8, 2)) continue;
-      const int tiles_m = (M + BM - 1) / BM;
-      if ((tiles_m * BM - M) * 4 > tiles_m * BM) continue;
-      // per_image 2: per-image tiles of whole output rows (tp = the rows of
-      // OW that fit BN; the columns past tp computed and dropped), whose
-      // patch has no partial rows: GoogLeNet conv2 (56 x 56) fits 8 pieces
-      // at 112-position tiles where 128-position ones need 9
-      for (int per_image = 0; per_image < 3; ++per_image) {
-        int rmax = 0, tpi = 0, octb = 0, tp = 0;
-        if (per_image == 0) {
-          rmax = patch_rows(N, HW, OW, OH, KH, BN, 3);
-          if (rmax < 0) continue;
-          octb = ((rmax * RPC + 2 * ((3 * OW * (1 - KH)) & 15)) * 16 + 255) / 256 * 256;
-        } else if (per_image == 1) {
-          tpi = (HW + BN - 1) / BN;
-          for (int t = 0; t < tpi; ++t) {
-            const int f = t * BN / OW, l = (std::min((t + 1) * BN, HW) - 1) / OW;
-            rmax = std::max(rmax, l - f + KH);
-          }
-          octb = (rmax * RPC * 16 + 255) / 256 * 256;
-        } else {
-          if (OW > BN || BN % OW == 0 || HW <= BN) continue;
-          // 64 x 128 tiles only: GoogLeNet conv2 0.875-0.886 ms there vs
-          // 0.943-0.963 on 128 x 128 (a quarter of the rows padded; equal
-          // estimates), profiles/r06_ab_cb_rowalign.txt
-          constexpr int kRowAlignWR = 2;
-          if (WR != kRowAlignWR) continue;
-          tp = BN / OW * OW;
-          tpi = (HW + tp - 1) / tp;
-          rmax = tp / OW + KH - 1;
-          octb = (rmax * RPC * 16 + 255) / 256 * 256;
-        }
-        if ((2 * octb / 16 + 255) / 256 > 8) continue;
-        const int tiles_n = per_image ? tpi * d->num : (N + BN - 1) / BN;
-        const int64_t nwg = (int64_t)G * tiles_m * tiles_n;
-        if (nwg >= (1ll << 31)) continue;
-        // a 64-row tile pays about a third more per MFMA (two waves read each
-        // weight fragment for half the columns): AlexNet conv5 (128 rows per
-        // group) 0.172 ms on 128 x 128 vs 0.184 on 64 x 128, while conv4
-        // (192 rows per group: 128-row tiles pad a quarter) 0.297 on its
-        // one-per-CU 64 x 256 plan vs 0.267 on 64 x 128
-        const int64_t cost = (nwg + 511) / 512 * 2 * BM * BN * (BM == 64 ? 4 : 3) / 3;
-        int64_t& bc = per_image == 2 ? best3 : best2;
-        CbPlan& pc = per_image == 2 ? p3 : p2;
+    cb_tiles(KH, 2, [&](int WR, int NB) {
+      for (int kind : {CB_CONTIG, CB_PERIMG, CB_ROWALIGN}) {
+        // row-aligned: GoogLeNet conv2 (56 x 56) fits 8 pieces at 112-position
+        // tiles where 128-position ones need 9.  64 x 128 tiles only:
+        // GoogLeNet conv2 0.875-0.886 ms there vs 0.943-0.963 on 128 x 128 (a
+        // quarter of the rows padded; equal estimates),
+        // profiles/r06_ab_cb_rowalign.txt
+        constexpr int kRowAlignWR = 2;
+        if (kind == CB_ROWALIGN && WR != kRowAlignWR) continue;
+        if (!cb_candidate(d, RPC, kind, WR, NB, 2, c, cost)) continue;
+        int64_t& bc = kind == CB_ROWALIGN ? best3 : best2;
         if (bc < 0 || cost < bc) {
           bc = cost;
-          pc = CbPlan{WR, NB, RPC, 8, octb, tiles_m, tiles_n, 2, tpi};
-          pc.tp = tp;
-          pc.kind = per_image == 2 ? CB_ROWALIGN : per_image == 1 ? CB_PERIMG : CB_CONTIG;
+          (kind == CB_ROWALIGN ? p3 : p2) = c;
         }
       }
-    }
+      return false;
+    });
     // Rounds x area prices a round of two workgroups like one of twice the
     // area, but measured the pair hides its waits: every AlexNet layer runs
     // faster there although its estimate is up to a third longer (conv3
@@ -2841,44 +2927,24 @@ bool conv_cb_plan(const rram_conv_desc* d, CbPlan& pl) {
 // conv2 (5x5, two workgroups per CU) 0.482 -> 0.457-0.461 ms, conv5 (3x3, two
 // per CU) 0.170 -> 0.166; at one workgroup per CU the 16x16x32 form lost
 // MFMA-busy (conv3 0.64 -> 0.59) faster than it gained clock.
-int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, const float* w, const float* bias,
-                   float* y, void* y_oct, int relu, hipStream_t s, const WPack& wk) {
-  CbPlan pl;
-  if (!conv_cb_plan(d, pl)) return 0;
+int conv_cb_x6_fwd(const rram_conv_desc* d, const CbPlan& pl, const float* x, const void* x_oct, const float* w,
+                   const float* bias, float* y, void* y_oct, int relu, hipStream_t s, const WPack& wk) {
   const bool use16 = pl.OCC == 2;
-  if (y_oct != nullptr && d->num_output % 8 != 0) return 0;
-  const int KH = d->kernel_h, KW = d->kernel_w, T = KH * KW;
+  RRAM_REQUIRE(y_oct == nullptr || d->num_output % 8 == 0, "conv: output octets need num_output %% 8 == 0");
+  const int KH = d->kernel_h, T = KH * d->kernel_w;
   const int G = d->group, Cg = d->channels / G, M = d->num_output / G;
   // the epilogue writes whole octets of one group's rows: a group whose row
   // count is not a multiple of 8 would share octets with its neighbour, so its
   // companion is packed from y after the kernel instead
   void* const y_oct_k = (y_oct != nullptr && M % 8 == 0) ? y_oct : nullptr;
   // y == nullptr (the convolution-output fold) needs the companion from the
-  // 16x16x32 epilogue itself
-  if (y == nullptr && !wk.query && (!use16 || y_oct_k == nullptr)) return 0;
+  // 16x16x32 epilogue itself (conv_x6_select: companion_only)
+  RRAM_REQUIRE(y != nullptr || wk.query != nullptr || (use16 && y_oct_k != nullptr),
+               "conv: y = NULL needs the octet companion from the epilogue");
   const int HW = d->out_h * d->out_w, HWi = d->height * d->width;
-  Params P{};
-  P.M = M;
-  P.N = d->num * HW;
-  P.K = Cg * T;
-  P.split = 1;
-  ConvGeom& cv = P.cv;
-  cv.C = Cg;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = KH;
-  cv.KW = KW;
-  cv.ph = d->pad_h;
-  cv.pw = d->pad_w;
-  cv.sh = cv.sw = cv.dh = cv.dw = 1;
-  cv.Ho = d->out_h;
-  cv.Wo = d->out_w;
-  cv.tpitch = pl.tp;
-  cv.howo = make_fastdiv(HW);
-  cv.wo_div = make_fastdiv(d->out_w);
-  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
-  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)d->num_output * HW;
-  P.e.hw = make_fastdiv(HW);
+  Params P = conv_params(d, wk, y, bias, relu);
+  conv_window(d, P.cv);
+  P.cv.tpitch = pl.tp;
   P.grp_c = (int64_t)M * HW;
   P.grp_bias = M;
   P.tiles_m = pl.tiles_m;
@@ -2890,33 +2956,26 @@ int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, c
   const int rblocks = pl.tiles_m * pl.WR;
   const int64_t wfrags =
       use16 ? (int64_t)G * rblocks * (((Cg / 16) * T + 1) / 2) * 2 : (int64_t)G * rblocks * (Cg / 16) * T;
-  if (wk.query) {
-    *wk.query = static_cast<size_t>(wfrags * 3072);
-    return 1;
-  }
-  const int64_t xb_al = x_oct != nullptr ? 0 : (xbytes + 255) / 256 * 256;
-  const int64_t scratch = xb_al + (wk.p ? 0 : wfrags * 3072);
-  char* buf = scratch > 0 ? reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(scratch / 4), s)) : nullptr;
-  RRAM_REQUIRE(scratch == 0 || buf != nullptr, "conv: packed-operand buffer allocation failed");
-  char* wbuf = wk.p ? static_cast<char*>(wk.p) : buf + xb_al;
-  int rc = 0;
-  if (x_oct == nullptr) {
-    rc = pack_octets(x, buf, d->num, d->channels, HWi, s);
-    if (rc) return rc;
-  }
-  if (!wk.valid) {
-    const int wunits = static_cast<int>(wfrags * 64);
-    if (use16)
-      hipLaunchKernelGGL(k_conv_cb16_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, wbuf, M, Cg, T,
-                         rblocks, wunits);
-    else
-      hipLaunchKernelGGL(k_conv_cb_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, wbuf, M, Cg, T,
-                         rblocks, wunits);
-    rc = launch_status("conv weight pack x6 (octets)");
-    if (rc) return rc;
-  }
+  char *wbuf = nullptr, *xbuf = nullptr;
+  int rc = conv_weight_pack(
+      wk, wfrags * 3072, s, "conv weight pack x6 (octets)",
+      [&](char* p) {
+        const int wunits = static_cast<int>(wfrags * 64);
+        if (use16)
+          hipLaunchKernelGGL(k_conv_cb16_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, p, M, Cg, T,
+                             rblocks, wunits);
+        else
+          hipLaunchKernelGGL(k_conv_cb_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, p, M, Cg, T, rblocks,
+                             wunits);
+      },
+      &wbuf, x_oct != nullptr ? 0 : (xbytes + 255) / 256 * 256,
+      [&](char* b) {
+        xbuf = b;
+        return x_oct != nullptr ? 0 : pack_octets(x, b, d->num, d->channels, HWi, s);
+      });
+  if (rc) return rc;
   const auto* wp = reinterpret_cast<const x6::bf16x8*>(wbuf);
-  const auto* xp = reinterpret_cast<const uint16_t*>(x_oct != nullptr ? x_oct : buf);
+  const auto* xp = reinterpret_cast<const uint16_t*>(x_oct != nullptr ? x_oct : xbuf);
   const int ximg = d->channels / 8 * HWi * 48;
   const unsigned nwg = static_cast<unsigned>((int64_t)G * pl.tiles_m * pl.tiles_n);
   const uint32_t xrange = static_cast<uint32_t>(xbytes);  // whole packed input (the kernel narrows it per group)
@@ -2940,13 +2999,11 @@ int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, c
                        pl.tpi);                                                                                     \
   } else
 #define RRAM_X(kh, wr, nb, pd, occ) RRAM_X2(kh, wr, nb, pd, occ, 0) RRAM_X2(kh, wr, nb, pd, occ, 1)
-    RRAM_CB16_LIST(RRAM_X) { return 0; }
+    RRAM_CB16_LIST(RRAM_X) RRAM_REQUIRE(false, "conv: the plan names a cb16 kernel that is not built");
 #undef RRAM_X
 #undef RRAM_X2
     rc = launch_status("conv cb16 x6");
-    if (rc == 0 && y_oct != nullptr && y_oct_k == nullptr) rc = pack_octets(y, y_oct, d->num, d->num_output, HW, s);
-    return rc ? rc : 1;
-  }
+  } else {
 #define RRAM_X(kh, wr, nb, pd, occ)                                                                           \
   if (KH == kh && pl.WR == wr && pl.NB == nb && pl.PD == pd && pl.OCC == occ) {                               \
     hipLaunchKernelGGL((k_conv_cb_x6<kh, kh, wr, nb, pd, occ>), dim3(nwg), dim3(256), 0, s, P, wp, xp, pl.octb,   \
@@ -2955,43 +3012,53 @@ int conv_cb_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, c
                        make_fastdiv(static_cast<uint32_t>(pl.octb >> 4)), make_fastdiv(static_cast<uint32_t>(pl.RPC)), \
                        pl.tpi);                                                                                \
   } else
-  RRAM_CB_LIST(RRAM_X) { return 0; }
+    RRAM_CB_LIST(RRAM_X) RRAM_REQUIRE(false, "conv: the plan names a cb kernel that is not built");
 #undef RRAM_X
-  rc = launch_status("conv cb x6");
+    rc = launch_status("conv cb x6");
+  }
   if (rc == 0 && y_oct != nullptr && y_oct_k == nullptr) rc = pack_octets(y, y_oct, d->num, d->num_output, HW, s);
   return rc ? rc : 1;
 }
 
-// ---- k_conv1x1_x6 plan ----
+// ---- k_conv1x1_x6 ----
 struct C1Plan {
   int MI, NB, WR, VEC, tiles_m, tiles_n;
 };
 // (MI, NB, WR): each the DMA form (VEC = 4 only: conv_1x1_dma) and the ring
 // form with VEC = 1.  The ring form with VEC = 4 runs only where M <= 64
 // (else conv_1x1_dma takes it), and conv_1x1_plan gives such an M no tile of
-// 32 MI WR >= 128 rows (half of it would pad): c1x1_ring_v4.
+// 32 MI WR >= 128 rows (half of it would pad): c1x1_ring_v4.  The planner
+// tries the tiles in this order, and ties go to the first.
 #define RRAM_C1X1_LIST(X) X(1, 2, 1) X(2, 1, 1) X(2, 2, 1) X(2, 1, 2) X(4, 1, 1) X(4, 2, 1) X(4, 1, 2) X(4, 2, 2)
+struct C1Form {
+  int MI, NB, WR;
+};
+constexpr C1Form kC1Forms[] = {
+#define RRAM_X(mi, nb, wr) {mi, nb, wr},
+    RRAM_C1X1_LIST(RRAM_X)
+#undef RRAM_X
+};
 constexpr bool c1x1_ring_v4(int mi, int wr) { return 32 * mi * wr <= 64; }
-bool conv_1x1_plan(const rram_conv_desc* d, const float* x, C1Plan& pl) {
+// x_align: what the input pointer is aligned to (16, 4, or less)
+bool conv_1x1_plan(const rram_conv_desc* d, int x_align, C1Plan& pl) {
   if (d->kernel_h != 1 || d->kernel_w != 1 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 0 ||
       d->pad_w != 0 || d->dilation_h != 1 || d->dilation_w != 1 || d->group != 1)
     return false;
   const int M = d->num_output, C = d->channels, HW = d->height * d->width;
   if (C % 16 != 0 || M < 1 || d->num < 1) return false;
   const int64_t N = (int64_t)d->num * HW;
-  if ((int64_t)d->num * C * HW * 4 >= (1ll << 31) || (int64_t)d->num * M * HW * 4 >= (1ll << 31)) return false;
-  if (x != nullptr && (reinterpret_cast<uintptr_t>(x) & 3u) != 0) return false;
-  const bool v4 = HW % 4 == 0 && (x == nullptr || (reinterpret_cast<uintptr_t>(x) & 15u) == 0);
+  if (!fits_i32((int64_t)d->num * C * HW, 4) || !fits_i32((int64_t)d->num * M * HW, 4)) return false;
+  if (x_align < 4) return false;
+  const bool v4 = HW % 4 == 0 && x_align >= 16;
   // least estimated time: MFMA makespan (rounds of 256 workgroups x tile work
   // at the bf16x6 rate of one CU) against the HBM stream (input once per M-tile)
-  static const int cfg[][3] = {{1, 2, 1}, {2, 1, 1}, {2, 2, 1}, {2, 1, 2}, {4, 1, 1}, {4, 2, 1}, {4, 1, 2}, {4, 2, 2}};
   double best = -1.0;
-  for (const auto& c : cfg) {
-    const int MI = c[0], NB = c[1], WR = c[2];
+  for (const C1Form& c : kC1Forms) {
+    const int MI = c.MI, NB = c.NB, WR = c.WR;
     const int BM = 32 * MI * WR, BN = 32 * NB * (4 / WR);
     if (BM > 32 && (BM / 2) >= M) continue;                  // half the tile would pad
     const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
-    if (tm * tn >= (1ll << 31)) continue;
+    if (!fits_i32(tm * tn)) continue;
     const double t_mfma = (double)((tm * tn + 255) / 256) * BM * BN * C * 2.0 / (416.7e12 / 256);
     const double t_mem = ((double)tm * N * C * 4 + (double)N * M * 4) / 5.0e12;
     const double t = std::max(t_mfma, t_mem) * (1.0 + 0.02 * (MI * NB == 8 ? 0 : 1));
@@ -3005,11 +3072,15 @@ bool conv_1x1_plan(const rram_conv_desc* d, const float* x, C1Plan& pl) {
 
 // the LDS-DMA form of the 1x1 kernel (else the register ring), see conv_1x1_x6_fwd
 bool conv_1x1_dma(const C1Plan& pl, int M) { return pl.VEC == 4 && M > 64; }
+bool c1x1_built(const C1Plan& pl, int M) {
+  for (const C1Form& f : kC1Forms)
+    if (pl.MI == f.MI && pl.NB == f.NB && pl.WR == f.WR)
+      return conv_1x1_dma(pl, M) || pl.VEC == 1 || c1x1_ring_v4(f.MI, f.WR);
+  return false;
+}
 
-int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* y_oct,
-                    int relu, hipStream_t s, const WPack& wk) {
-  C1Plan pl;
-  if (!conv_1x1_plan(d, wk.query ? nullptr : x, pl)) return 0;
+int conv_1x1_x6_fwd(const rram_conv_desc* d, const C1Plan& pl, const float* x, const float* w, const float* bias,
+                    float* y, void* y_oct, int relu, hipStream_t s, const WPack& wk) {
   const int M = d->num_output, C = d->channels, HW = d->height * d->width;
   // y = NULL (the convolution-output fold): the epilogue writes the companion alone
   RRAM_REQUIRE(y != nullptr || wk.query != nullptr || (y_oct != nullptr && M % 8 == 0),
@@ -3017,32 +3088,20 @@ int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, con
   const int BMc = 32 * pl.MI * pl.WR;
   const int rblocks = pl.tiles_m * (BMc / 32);
   const int64_t wfrags = (int64_t)rblocks * (C / 16);
-  if (wk.query) {
-    *wk.query = static_cast<size_t>(wfrags * 3072);
-    return 1;
-  }
-  Params P{};
-  P.M = M;
-  P.N = d->num * HW;
-  P.K = C;
-  P.split = 1;
-  P.cv.C = C;
-  P.cv.howo = make_fastdiv(HW);
-  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
-  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)M * HW;
-  P.e.hw = make_fastdiv(HW);
+  char* wbuf = nullptr;
+  if (const int rc = conv_weight_pack(
+          wk, wfrags * 3072, s, "conv 1x1 weight pack x6",
+          [&](char* p) {
+            const int wunits = static_cast<int>(wfrags * 64);
+            hipLaunchKernelGGL(k_conv_cb_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, p, M, C, 1, rblocks,
+                               wunits);
+          },
+          &wbuf))
+    return rc;
+  Params P = conv_params(d, wk, y, bias, relu);
   P.tiles_m = pl.tiles_m;
   P.tiles_n = pl.tiles_n;
   P.tiles_z = 1;
-  char* wbuf = wk.p ? static_cast<char*>(wk.p) : reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(wfrags * 768), s));
-  RRAM_REQUIRE(wbuf != nullptr, "conv 1x1: packed-weight buffer allocation failed");
-  if (!wk.valid) {
-    const int wunits = static_cast<int>(wfrags * 64);
-    hipLaunchKernelGGL(k_conv_cb_pack_x6, dim3(stream_blocks(wunits)), dim3(256), 0, s, w, wbuf, M, C, 1, rblocks,
-                       wunits);
-    const int rc = launch_status("conv 1x1 weight pack x6");
-    if (rc) return rc;
-  }
   const auto* wp = reinterpret_cast<const x6::bf16x8*>(wbuf);
   const uint32_t xrange = static_cast<uint32_t>((int64_t)d->num * C * HW * 4);
   const unsigned nwg = static_cast<unsigned>((int64_t)pl.tiles_m * pl.tiles_n);
@@ -3066,201 +3125,161 @@ int conv_1x1_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, con
       hipLaunchKernelGGL((k_conv1x1_x6<mi, nb, wr, 4>), dim3(nwg), dim3(256), 0, s, P, wp, x, xrange, yo,   \
                          cout8);                                                                            \
     else                                                                                                    \
-      return 0;                                                                                             \
+      RRAM_REQUIRE(false, "conv 1x1: the plan names a ring form that is not built");                        \
   } else
-  RRAM_C1X1_LIST(RRAM_X) { return 0; }
+  RRAM_C1X1_LIST(RRAM_X) RRAM_REQUIRE(false, "conv 1x1: the plan names a tile that is not built");
 #undef RRAM_X
   int rc = launch_status("conv 1x1 x6");
   if (rc == 0 && y_oct != nullptr && yo == nullptr) rc = pack_octets(y, y_oct, d->num, M, HW, s);
   return rc ? rc : 1;
 }
 
-int conv_patch_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,
-                      hipStream_t s, const WPack& wk);
+// ---- which kernel a descriptor gets ----
+// The one record of the forward dispatch: the first family, in the order of
+// this enum, whose planner takes d and names a built kernel, with that
+// family's plan.  conv_x6_fwd launches from it (the pack-bytes query
+// included), conv_fwd_kernel_id and a kernel-id query only print it.
+enum ConvFamily { FAM_NONE = 0, FAM_CB, FAM_C1X1, FAM_RING, FAM_S2, FAM_PATCH };
+struct ConvSel {
+  ConvFamily family = FAM_NONE;
+  CbPlan cb{};
+  C1Plan c1{};
+  ConvPlan patch{};
+};
+// x_align: as conv_1x1_plan's.  companion_only: the call has no y (the
+// convolution-output fold), which of the channel-octet kernels only the
+// 16x16x32 epilogue serves, on groups of whole octets; any other plan of
+// theirs passes d on to the later families.
+ConvSel conv_x6_select(const rram_conv_desc* d, int x_align, bool companion_only = false) {
+  ConvSel sel;
+  const int KH = d->kernel_h;
+  if (conv_cb_plan(d, sel.cb) && cb_built(KH, sel.cb.WR, sel.cb.NB, sel.cb.PD, sel.cb.OCC) &&
+      (!companion_only || (sel.cb.OCC == 2 && (d->num_output / d->group) % 8 == 0)))
+    sel.family = FAM_CB;
+  else if (conv_1x1_plan(d, x_align, sel.c1) && c1x1_built(sel.c1, d->num_output))
+    sel.family = FAM_C1X1;
+  else if (conv1_ring_ok(d))
+    sel.family = FAM_RING;
+  else if (conv_s2_ok(d))
+    sel.family = FAM_S2;
+  else if (conv_x6_plan(d, sel.patch) && patch_built(KH, sel.patch.CPH, sel.patch.PD))
+    sel.family = FAM_PATCH;
+  return sel;
+}
+
+// the selected kernel's id (rram_conv_fwd_kernel_id), "f32" for FAM_NONE
+std::string conv_sel_id(const rram_conv_desc* d, const ConvSel& sel) {
+  char b[64];
+  const int KH = d->kernel_h;
+  const CbPlan& cb = sel.cb;
+  const C1Plan& c1 = sel.c1;
+  static const char* const kinds[] = {"contig", "perimg", "rowalign", "whole"};
+  switch (sel.family) {
+    case FAM_CB:
+      if (cb.OCC == 2)
+        snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC,
+                 (d->channels / d->group / 16) & 1, kinds[cb.kind]);
+      else
+        snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC, kinds[cb.kind]);
+      return b;
+    case FAM_C1X1:
+      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>", conv_1x1_dma(c1, d->num_output) ? "c1x1_dma" : "c1x1", c1.MI, c1.NB,
+               c1.WR, c1.VEC);
+      return b;
+    case FAM_RING:
+      return "conv1_ring<227>";
+    case FAM_S2:
+      snprintf(b, sizeof b, "conv_s2<%d>", kS2Nbw);
+      return b;
+    case FAM_PATCH:
+      snprintf(b, sizeof b, "patch<%d,%d,%d,%d>", KH, sel.patch.CPH, sel.patch.MI, sel.patch.PD);
+      return b;
+    case FAM_NONE:
+      break;
+  }
+  return "f32";
+}
+
+// The id of the kernel conv_x6_fwd launches for d with a dense y; x_align16 =
+// 0 plans the 1x1 kernels for an input that is only 4-byte aligned.
+std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16) {
+  if (f32_engine().load(std::memory_order_relaxed) != RRAM_ENGINE_BF16X6) return "f32";
+  return conv_sel_id(d, conv_x6_select(d, x_align16 ? 16 : 4));
+}
+
 // The bf16x6 convolution forward.  x_oct: NULL or the octet companion of x
 // (k_pack_octets_x6 layout; the channel-octet kernel then skips its input
 // pack); y_oct: NULL or a buffer that receives y's octet companion (written
-// by the channel-octet kernel's epilogue, else packed from y afterwards).
-// Returns 1 when it ran, 0 when not covered (nothing written), < 0 on error.
+// by the channel-octet and 1x1 kernels' epilogues, else packed from y
+// afterwards).  Returns 1 when it ran, 0 when not covered (nothing written),
+// < 0 on error.
 int conv_x6_fwd(const rram_conv_desc* d, const float* x, const void* x_oct, const float* w, const float* bias,
                 float* y, void* y_oct, int relu, hipStream_t s, const WPack& wk) {
   if (f32_engine().load(std::memory_order_relaxed) != RRAM_ENGINE_BF16X6) return 0;
-  if (wk.query == nullptr && (reinterpret_cast<uintptr_t>(w) & 3u) != 0) return 0;
+  const bool query = wk.query != nullptr;
+  if (!query && (reinterpret_cast<uintptr_t>(w) & 3u) != 0) return 0;
   // the epilogues' 32-bit output offsets also hold a strided (Concat-slice) image stride
-  if (wk.y_img > 0 && (int64_t)d->num * wk.y_img * 4 >= (1ll << 31)) return 0;
-  if (planning()) {  // a kernel-id query: one line naming the kernel the calls below would launch
-    const std::string id = conv_fwd_kernel_id(d, (reinterpret_cast<uintptr_t>(x) & 15u) == 0);
-    return id != "f32" && plan_note("x6:%s", id.c_str()) ? 1 : 0;
+  if (wk.y_img > 0 && !fits_i32((int64_t)d->num * wk.y_img, 4)) return 0;
+  const uintptr_t xa = reinterpret_cast<uintptr_t>(x);
+  if (planning()) {  // a kernel-id query: one line naming the kernel the call would launch for a dense y
+    const ConvSel sel = conv_x6_select(d, (xa & 15u) == 0 ? 16 : 4);
+    return sel.family != FAM_NONE && plan_note("x6:%s", conv_sel_id(d, sel).c_str()) ? 1 : 0;
   }
-  {
-    const int rc = conv_cb_x6_fwd(d, x, x_oct, w, bias, y, y_oct, relu, s, wk);
-    if (rc != 0) return rc;
-  }
-  {
-    const int rc1 = conv_1x1_x6_fwd(d, x, w, bias, y, y_oct, relu, s, wk);  // writes y_oct itself
-    if (rc1 != 0) return rc1;
-  }
+  // (a pack-bytes query has no x: it plans for an aligned one)
+  const ConvSel sel = conv_x6_select(d, query || (xa & 15u) == 0 ? 16 : (xa & 3u) == 0 ? 4 : 0, y == nullptr && !query);
   // only the channel-octet and 1x1 kernels' epilogues write a companion without y
-  RRAM_REQUIRE(y != nullptr || wk.query != nullptr,
+  RRAM_REQUIRE(y != nullptr || query || sel.family == FAM_CB || sel.family == FAM_C1X1,
                "conv: y = NULL needs a companion-writing epilogue (rram_conv_output_octets_only)");
-  int rc = conv_wide_x6_fwd(d, x, w, bias, y, relu, s, wk);
-  if (rc == 0) rc = conv_s2_x6_fwd(d, x, w, bias, y, relu, s, wk);
-  if (rc == 0) rc = conv_patch_x6_fwd(d, x, w, bias, y, relu, s, wk);
-  if (wk.query) return rc;
-  if (rc > 0 && y_oct != nullptr) {
+  int rc = 0;
+  switch (sel.family) {
+    case FAM_NONE:
+      return 0;
+    case FAM_CB:  // (these two see to y_oct themselves)
+      return conv_cb_x6_fwd(d, sel.cb, x, x_oct, w, bias, y, y_oct, relu, s, wk);
+    case FAM_C1X1:
+      return conv_1x1_x6_fwd(d, sel.c1, x, w, bias, y, y_oct, relu, s, wk);
+    case FAM_RING:
+      rc = conv_wide_x6_fwd(d, x, w, bias, y, relu, s, wk);
+      break;
+    case FAM_S2:
+      rc = conv_s2_x6_fwd(d, x, w, bias, y, relu, s, wk);
+      break;
+    case FAM_PATCH:
+      rc = conv_patch_x6_fwd(d, sel.patch, x, w, bias, y, relu, s, wk);
+      break;
+  }
+  if (rc > 0 && !query && y_oct != nullptr) {
     const int pr = pack_octets(y, y_oct, d->num, d->num_output, d->out_h * d->out_w, s);
     if (pr) return pr;
   }
   return rc;
 }
 
-int conv_patch_x6_fwd(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,
-                      hipStream_t s, const WPack& wk) {
-  ConvPlan pl;
-  if (!conv_x6_plan(d, pl)) return 0;
-  const int KH = d->kernel_h, KW = d->kernel_w;
-  const int G = d->group, Cg = d->channels / G, M = d->num_output / G;
-  const int HW = d->out_h * d->out_w, OW = d->out_w, OH = d->out_h;
-  const int CPH = pl.CPH, MI = pl.MI, mt = pl.mt, PW = pl.PW, CS = pl.CS, PD = pl.PD;
-  Params P{};
-  P.M = M;
-  P.N = d->num * HW;
-  P.K = Cg * KH * KW;
-  P.split = 1;
-  P.b = make_view(x, 0, P.N, P.K);
-  ConvGeom& cv = P.cv;
-  cv.C = Cg;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = KH;
-  cv.KW = KW;
-  cv.ph = d->pad_h;
-  cv.pw = d->pad_w;
-  cv.sh = cv.sw = cv.dh = cv.dw = 1;
-  cv.Ho = OH;
-  cv.Wo = OW;
-  cv.howo = make_fastdiv(HW);
-  cv.wo_div = make_fastdiv(OW);
-  cv.chw = (int64_t)d->channels * d->height * d->width;
-  cv.in_bytes = static_cast<int>((int64_t)d->num * cv.chw * 4);
-  P.e = make_epi(y, HW, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
-  P.e.cimg = wk.y_img > 0 ? wk.y_img : (int64_t)d->num_output * HW;
-  P.e.hw = make_fastdiv(HW);
-  P.grp_b = (int64_t)Cg * d->height * d->width;
-  P.grp_c = (int64_t)M * HW;
-  P.grp_bias = M;
-  const int T = KH * KW, S = CPH * T, G8 = (S + 7) / 8, RLH = (G8 * 96 + 16) / 2;
-  const int BMc = 32 * MI, tiles_m = mt / BMc, ktiles = Cg / (2 * CPH);
-  const int64_t total = (int64_t)G * tiles_m * ktiles * BMc * RLH;
-  if (wk.query) {
-    *wk.query = static_cast<size_t>(total * 2);
-    return 1;
-  }
-  uint16_t* wp = reinterpret_cast<uint16_t*>(wk.p ? wk.p : pack_buffer(static_cast<size_t>((total + 1) / 2), s));
-  RRAM_REQUIRE(wp != nullptr, "conv: packed-weight buffer allocation failed");
-  int rc = 0;
-  if (!wk.valid) {
-    const int units = G * tiles_m * ktiles * BMc * G8 * 2;
-    hipLaunchKernelGGL(k_conv_patch_pack_x6, dim3(stream_blocks(units)), dim3(256), 0, s, w,
-                       reinterpret_cast<char*>(wp), G, M, Cg, T, CPH, G8, 2 * RLH, BMc, tiles_m, ktiles, units);
-    rc = launch_status("conv weight pack x6");
-    if (rc) return rc;
-  }
-#define RRAM_P(KH_, CPH_, PD_)                                                                           \
-  if (KH == KH_ && CPH == CPH_ && PD == PD_)                                                             \
-    rc = MI == 3 ? launch_patch_x6<KH_, CPH_, 3, PD_>(P, wp, PW, CS, G, s)                               \
-                 : launch_patch_x6<KH_, CPH_, 4, PD_>(P, wp, PW, CS, G, s);                              \
-  else
-  RRAM_PATCH_LIST(RRAM_P)
-  return 0;
-#undef RRAM_P
-  return rc ? rc : 1;
-}
-
-
-// ---- which forward kernel a descriptor selects (rram_conv_fwd_kernel_id) ----
-// The id of the kernel conv_x6_fwd launches for d with a dense y, from the
-// launch paths' own plans in conv_x6_fwd's order; x_align16 = 0 plans the 1x1
-// kernels for an input that is only 4-byte aligned.
-std::string conv_fwd_kernel_id(const rram_conv_desc* d, bool x_align16) {
-  char b[64];
-  if (f32_engine().load(std::memory_order_relaxed) != RRAM_ENGINE_BF16X6) return "f32";
-  const int KH = d->kernel_h;
-  CbPlan cb;
-  if (conv_cb_plan(d, cb) && cb_instantiated(KH, cb.WR, cb.NB, cb.PD, cb.OCC)) {
-    static const char* const kinds[] = {"contig", "perimg", "rowalign", "whole"};
-    if (cb.OCC == 2)
-      snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC,
-               (d->channels / d->group / 16) & 1, kinds[cb.kind]);
-    else
-      snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>/%s", KH, cb.WR, cb.NB, cb.PD, cb.OCC, kinds[cb.kind]);
-    return b;
-  }
-  C1Plan c1;
-  // (the plan only looks at the pointer's low bits: 4 = aligned to 4 bytes, not 16)
-  if (conv_1x1_plan(d, x_align16 ? nullptr : reinterpret_cast<const float*>(uintptr_t{4}), c1)) {
-    const bool dma = conv_1x1_dma(c1, d->num_output);
-    bool inst = false;
-#define RRAM_X(mi, nb, wr) \
-  inst = inst || (c1.MI == mi && c1.NB == nb && c1.WR == wr && (dma || c1.VEC == 1 || c1x1_ring_v4(mi, wr)));
-    RRAM_C1X1_LIST(RRAM_X)
-#undef RRAM_X
-    if (inst) {
-      snprintf(b, sizeof b, "%s<%d,%d,%d;v%d>", dma ? "c1x1_dma" : "c1x1", c1.MI, c1.NB, c1.WR, c1.VEC);
-      return b;
-    }
-  }
-  if (conv1_ring_ok(d)) return "conv1_ring<227>";
-  if (conv_s2_ok(d)) {
-    snprintf(b, sizeof b, "conv_s2<%d>", kS2Nbw);
-    return b;
-  }
-  ConvPlan pp;
-  if (conv_x6_plan(d, pp)) {
-    bool inst = false;
-#define RRAM_X(kh, cph, pd) inst = inst || (KH == kh && pp.CPH == cph && pp.PD == pd);
-    RRAM_PATCH_LIST(RRAM_X)
-#undef RRAM_X
-    if (inst) {
-      snprintf(b, sizeof b, "patch<%d,%d,%d,%d>", KH, pp.CPH, pp.MI, pp.PD);
-      return b;
-    }
-  }
-  return "f32";
-}
-
 // every instantiated forward kernel, one id per line (no tiling kind)
 std::string conv_fwd_kernel_list() {
   std::string out;
   char b[64];
-#define RRAM_X(kh, wr, nb, pd, occ)                                     \
-  snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>\n", kh, wr, nb, pd, occ); \
-  out += b;
-  RRAM_CB_LIST(RRAM_X)
-#undef RRAM_X
-#define RRAM_X(kh, wr, nb, pd, occ)                                                  \
-  for (int k = 0; k < 2; ++k) {                                                      \
-    snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>\n", kh, wr, nb, pd, occ, k);     \
-    out += b;                                                                        \
+  for (const CbForm& f : kCbForms)
+    for (int k = 0; k < f.OCC; ++k) {  // the 16x16x32 forms: both K-tile parities
+      if (f.OCC == 2)
+        snprintf(b, sizeof b, "cb16<%d,%d,%d,%d,%d;k%d>\n", f.KH, f.WR, f.NB, f.PD, f.OCC, k);
+      else
+        snprintf(b, sizeof b, "cb<%d,%d,%d,%d,%d>\n", f.KH, f.WR, f.NB, f.PD, f.OCC);
+      out += b;
+    }
+  for (const C1Form& f : kC1Forms) {
+    if (c1x1_ring_v4(f.MI, f.WR)) {
+      snprintf(b, sizeof b, "c1x1<%d,%d,%d;v4>\n", f.MI, f.NB, f.WR);
+      out += b;
+    }
+    snprintf(b, sizeof b, "c1x1<%d,%d,%d;v1>\nc1x1_dma<%d,%d,%d;v4>\n", f.MI, f.NB, f.WR, f.MI, f.NB, f.WR);
+    out += b;
   }
-  RRAM_CB16_LIST(RRAM_X)
-#undef RRAM_X
-#define RRAM_X(mi, nb, wr)                                                            \
-  if (c1x1_ring_v4(mi, wr)) {                                                         \
-    snprintf(b, sizeof b, "c1x1<%d,%d,%d;v4>\n", mi, nb, wr);                         \
-    out += b;                                                                         \
-  }                                                                                   \
-  snprintf(b, sizeof b, "c1x1<%d,%d,%d;v1>\nc1x1_dma<%d,%d,%d;v4>\n", mi, nb, wr, mi, nb, wr); \
-  out += b;
-  RRAM_C1X1_LIST(RRAM_X)
-#undef RRAM_X
-#define RRAM_X(kh, cph, pd)                                            \
-  for (int mi : {3, 4}) {                                              \
-    snprintf(b, sizeof b, "patch<%d,%d,%d,%d>\n", kh, cph, mi, pd);    \
-    out += b;                                                          \
-  }
-  RRAM_PATCH_LIST(RRAM_X)
-#undef RRAM_X
+  for (const PatchForm& f : kPatchForms)
+    for (int mi : {3, 4}) {
+      snprintf(b, sizeof b, "patch<%d,%d,%d,%d>\n", f.KH, f.CPH, mi, f.PD);
+      out += b;
+    }
   out += "conv1_ring<227>\n";
   snprintf(b, sizeof b, "conv_s2<%d>\n", kS2Nbw);
   out += b;
@@ -3399,7 +3418,7 @@ int rram_f32_engine_for_conv(const rram_conv_desc* d) {
   rram::C1Plan c1;
   return rram::f32_engine().load() == RRAM_ENGINE_BF16X6 &&
                  (rram::conv_x6_plan(d, pl) || rram::conv1_ring_ok(d) || rram::conv_s2_ok(d) ||
-                  rram::conv_cb_plan(d, cpl) || rram::conv_1x1_plan(d, nullptr, c1))
+                  rram::conv_cb_plan(d, cpl) || rram::conv_1x1_plan(d, 16, c1))
              ? RRAM_ENGINE_BF16X6
              : RRAM_ENGINE_F32;
 }
@@ -3423,7 +3442,7 @@ int rram_conv_fwd_kernel_id(const rram_conv_desc* d_in, int x_align16, char* out
   rram_conv_desc d = *d_in;
   const int rc = rram_conv_out_shape(&d);
   if (rc) return rc;
-  RRAM_REQUIRE((int64_t)d.num * d.out_h * d.out_w < (1ll << 31), "kernel id query: too many output positions");
+  RRAM_REQUIRE(rram::fits_i32((int64_t)d.num * d.out_h * d.out_w), "kernel id query: too many output positions");
   return copy_text(d.num == 0 ? std::string("none") : rram::conv_fwd_kernel_id(&d, x_align16 != 0), out, cap);
 }
 
@@ -3436,7 +3455,7 @@ int rram_conv_output_octets_only(const rram_conv_desc* d_in) {
   if (rram_conv_out_shape(&d) != RRAM_OK || d.num == 0 || d.num_output % 8 != 0) return 0;
   // the 1x1 kernels write the companion from their epilogue (whole octets)
   rram::C1Plan c1;
-  if (rram::conv_1x1_plan(&d, nullptr, c1)) return 1;
+  if (rram::conv_1x1_plan(&d, 16, c1)) return 1;
   rram::CbPlan pl;
   if (!rram::conv_cb_plan(&d, pl)) return 0;
   return pl.OCC == 2 && (d.num_output / d.group) % 8 == 0 ? 1 : 0;

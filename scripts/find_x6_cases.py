@@ -13,6 +13,7 @@ ops.conv_fwd_kernel_list() that no shape selected are listed as UNREACHED.
 
   python scripts/find_x6_cases.py            # print the table
   python scripts/find_x6_cases.py --write    # and rewrite tests/_x6_cases.py
+  python scripts/find_x6_cases.py --dump F   # every planner answer per candidate (to diff two builds)
 
 The boxes (SEARCH_BOX in tests/_x6_cases.py describes them):
 """
@@ -110,10 +111,42 @@ def reason(kid, above):
     return "the planner chose it for no shape of the box: " + box
 
 
+# descriptors on either side of each family's 2 GB guard (ring, s2, cb packed input, 1x1, patch output)
+GUARDS = [dict(x=(n, c, h, w), cout=m, k=k, s=s, p=p, g=1, align16=True)
+          for (c, h, w, m, k, s, p), ns in [((3, 227, 227, 96, 11, 4, 0), (1848, 1849, 1850)),
+                                            ((3, 224, 224, 64, 7, 2, 3), (668, 669)),
+                                            ((256, 13, 13, 128, 3, 1, 1), (8272, 8273)),
+                                            ((64, 56, 56, 64, 1, 1, 0), (2674, 2675)),
+                                            ((8, 64, 64, 128, 3, 1, 1), (1023, 1024))] for n in ns]
+
+
+def dump(path):
+    """One line per descriptor with everything the host dispatch answers for
+    it: two builds whose files are equal plan every shape alike."""
+    def line(cs):
+        d = XC.desc(cs)
+        ids = [ops.conv_fwd_kernel_id(d, al) for al in (True, False)]
+        nbytes, plan = ops.conv_weight_pack_bytes(d), ops.conv_octet_plan(d)
+        assert (nbytes > 0) == (ids[0] != "f32"), (cs, ids, nbytes)
+        return " ".join(map(str, [*cs["x"], cs["cout"], cs["k"], cs["s"], cs["p"], cs["g"], *ids, nbytes,
+                                  ",".join(map(str, plan.values())) if plan else "-", ops.conv_output_octets_only(d),
+                                  ops.conv_input_octets(d), ops.f32_engine_for_conv(d)])) + "\n"
+    with open(path, "w") as f:
+        n = sum(f.write(line(cs)) > 0 for cs in itertools.chain(candidates(), GUARDS, XC.X6_CASES)
+                if min(cs["x"][2:]) + 2 * cs["p"] >= cs["k"])
+        prev = ops.set_f32_engine(ops.ENGINE_F32)
+        n += sum(f.write(line(cs)) > 0 for cs in XC.X6_CASES)
+        ops.set_f32_engine(prev)
+    print(f"# {n} descriptors dumped to {path}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--write", action="store_true", help="rewrite the generated block of tests/_x6_cases.py")
+    ap.add_argument("--dump", metavar="FILE", help="write every planner answer per candidate descriptor and exit")
     a = ap.parse_args()
+    if a.dump:
+        return dump(a.dump)
     table, missing, above = search()
     body = "# instantiations no shape of the box selects: id -> reason\nUNREACHED = " + \
         pprint.pformat({k: reason(k, above) for k in missing}, width=118) + \
