@@ -1,6 +1,7 @@
 // C-ABI entry points for GEMM / GEMV / convolution / InnerProduct.
 // The heavy lifting is in gemm.hip (MFMA core) — this file validates
 // arguments, computes Caffe's shape rules and sequences the backward passes.
+#include <algorithm>
 #include <atomic>
 
 #include "rram_common.hpp"
@@ -312,6 +313,22 @@ size_t bwd_part_bytes(const rram_conv_desc& d, int imgs) {
 size_t col_bytes(const rram_conv_desc& d, int imgs) {
   return ((size_t)d.channels * d.kernel_h * d.kernel_w + 1) * (size_t)imgs * d.out_h * d.out_w * sizeof(float);
 }
+// The column path's share of ws_bytes: the largest image chunk (0: not even one
+// image fits) whose column buffer + weight-gradient partials (want_dw) fit, the
+// partials' offset (256-byte aligned) and bytes (0: no split-K, none wanted or no room)
+struct BwdColPlan { int chunk; size_t col_bytes_rounded, part_bytes; };
+static BwdColPlan bwd_col_plan(const rram_conv_desc& d, size_t ws_bytes, bool want_dw) {
+  const size_t per_img = col_bytes(d, 1);
+  int chunk = static_cast<int>(std::min<size_t>(ws_bytes / per_img, d.num));
+  if (chunk < 1) return {0, 0, 0};
+  size_t part = want_dw ? bwd_part_bytes(d, chunk) : 0;
+  while (chunk > 1 && col_bytes(d, chunk) + part > ws_bytes) {
+    --chunk;
+    part = bwd_part_bytes(d, chunk);
+  }
+  const size_t col = (col_bytes(d, chunk) + 255) / 256 * 256;
+  return {chunk, col, col + part <= ws_bytes ? part : 0};
+}
 }  // namespace
 
 size_t rram_conv2d_bwd_workspace(const rram_conv_desc* d_in, int images_per_chunk) {
@@ -351,17 +368,8 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
   // the workspace holds its split-K partials; else the column path below.
   const bool im2t = dw && x && w && ws && conv_bwd_weight_im2t_ok(&d, ws_bytes);
   bool fold_db = im2t && db && d.group == 1;
-  if (!im2t && db && dw && x && w && ws && d.group == 1 && HoWo >= 2 * 32) {
-    const size_t per_img = col_bytes(d, 1);
-    int chunk = ws_bytes >= per_img ? static_cast<int>(ws_bytes / per_img) : 0;
-    if (chunk > d.num) chunk = d.num;
-    size_t pb = chunk > 0 ? bwd_part_bytes(d, chunk) : 0;
-    while (chunk > 1 && col_bytes(d, chunk) + pb > ws_bytes) {
-      --chunk;
-      pb = bwd_part_bytes(d, chunk);
-    }
-    fold_db = chunk >= 1 && pb > 0 && (col_bytes(d, chunk) + 255) / 256 * 256 + pb <= ws_bytes;
-  }
+  if (!im2t && db && dw && x && w && ws && d.group == 1 && HoWo >= 2 * 32)
+    fold_db = bwd_col_plan(d, ws_bytes, true).part_bytes > 0;
   if (db && !fold_db) {
     const int S = d.num < 64 ? d.num : 64;
     if (ws && S > 1 && ws_bytes >= (size_t)d.num_output * S * sizeof(float)) {
@@ -427,29 +435,19 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
   if (!dw && !dx) return RRAM_OK;
   if (dx_fwd && !dw) return dx_as_fwd();
   const size_t per_img = col_bytes(d, 1);
-  RRAM_REQUIRE(ws != nullptr && ws_bytes >= per_img, "conv2d_bwd: workspace needs >= %zu bytes",
-               per_img);
-  // the largest image chunk whose col buffer + weight-gradient partials fit
-  int chunk = static_cast<int>(ws_bytes / per_img);
-  if (chunk > d.num) chunk = d.num;
-  size_t part_bytes = dw ? bwd_part_bytes(d, chunk) : 0;
-  while (chunk > 1 && col_bytes(d, chunk) + part_bytes > ws_bytes) {
-    --chunk;
-    part_bytes = bwd_part_bytes(d, chunk);
-  }
-  if (col_bytes(d, chunk) + part_bytes > ws_bytes) part_bytes = 0;  // no split-K
+  RRAM_REQUIRE(ws != nullptr && ws_bytes >= per_img, "conv2d_bwd: workspace needs >= %zu bytes", per_img);
+  const BwdColPlan plan = bwd_col_plan(d, ws_bytes, dw != nullptr);
   float* col = static_cast<float*>(ws);
-  void* part = part_bytes ? static_cast<char*>(ws) + (col_bytes(d, chunk) + 255) / 256 * 256 : nullptr;
-  if (part && (col_bytes(d, chunk) + 255) / 256 * 256 + part_bytes > ws_bytes) part = nullptr;
+  void* part = plan.part_bytes ? static_cast<char*>(ws) + plan.col_bytes_rounded : nullptr;
   const int64_t chw = (int64_t)d.channels * d.height * d.width;
   const int64_t ohw = (int64_t)d.num_output * HoWo;
-  for (int n0 = 0; n0 < d.num; n0 += chunk) {
-    const int nimg = (d.num - n0) < chunk ? (d.num - n0) : chunk;
+  for (int n0 = 0; n0 < d.num; n0 += plan.chunk) {
+    const int nimg = std::min(d.num - n0, plan.chunk);
     const int64_t ldcol = (int64_t)nimg * HoWo;
     if (dw) {
       rc = im2col_core(x + n0 * chw, chw, nimg, &d, col, ldcol, s, fold_db ? 1 : 0);
       if (rc) return rc;
-      rc = conv_bwd_weight_core(&d, nimg, dy + n0 * ohw, col, ldcol, dw, part, part ? part_bytes : 0, s,
+      rc = conv_bwd_weight_core(&d, nimg, dy + n0 * ohw, col, ldcol, dw, part, plan.part_bytes, s,
                                 fold_db ? db : nullptr);
       if (rc) return rc;
     }

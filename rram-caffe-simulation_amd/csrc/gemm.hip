@@ -1292,28 +1292,37 @@ int launch_cfg(Params P, int gz, hipStream_t s) {
   return launch_status("gemm");
 }
 
-// Tile choice.  BN = 128 with BM in {192, 128, 96, 64} picked to minimise the
-// padded rows of M (AlexNet: conv1 M = 96, conv4 M = 192 per group) as long as
-// the grid keeps >= 2 blocks per CU; 64x64 when even that grid is too small.
-// force_big: split-K grids (128x128).
+// The tile of a row-major split-K grid (the dense products and the weight
+// gradients; the convolution forward's split keeps launch_tiles' policy):
+// 128 x 128, or the two thin tiles below.  IM2T (the gathered weight gradient,
+// always split) has only these three tiles built: split_tile() names them.
+template <int AM, int BMODE, int OM, int KB>
+int launch_split(const Params& P, int gz, hipStream_t s) {
+  // M <= 32 and N > 64 (the CIFAR-10 weight gradients: Cout = 32, N = 76 /
+  // 801): 32 x 128 tiles, which waste no MFMA rows (64 x 64 padded half): C4
+  // 0.362 -> 0.348 ms per iteration.  Not for N <= 64 (LeNet conv1, N = 26:
+  // 0.199 -> 0.204 ms, the 128-wide B tile gathers mostly padding),
+  // profiles/r05_ab_split_thin32.txt
+  if constexpr (KB == 32) {
+    if (P.M <= 32 && P.N > 64) return launch_cfg<1, 4, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
+  }
+  // 64 x 64 tiles when an operand is that thin (conv weight gradients)
+  if (P.M <= 64 || P.N <= 64) return launch_cfg<2, 2, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
+  return launch_cfg<2, 2, 2, 2, AM, BMODE, OM, KB>(P, gz, s);
+}
+constexpr bool split_tile(int rows, int cols) {
+  return (rows == 32 && cols == 128) || (rows == 64 && cols == 64) || (rows == 128 && cols == 128);
+}
+
+// Tile choice of an unsplit grid.  BN = 128 with BM in {192, 128, 96, 64}
+// picked to minimise the padded rows of M (AlexNet: conv1 M = 96, conv4 M = 192
+// per group) as long as the grid keeps >= 2 blocks per CU; 64x64 when even
+// that grid is too small.
 // pz (0: gz): the z extent the tile policy sees; the map-group GEMM
 // (gemm_groups_core) launches gz = groups and keeps one group's tiles (pz = 1).
 template <int AM, int BMODE, int OM, int KB>
-int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
+int launch_tiles(const Params& P, int gz, hipStream_t s, int pz = 0) {
   if (pz <= 0) pz = gz;
-  if (force_big) {
-    // split-K grids with M <= 32 and N > 64 (the CIFAR-10 weight gradients:
-    // Cout = 32, N = 76 / 801): 32 x 128 tiles, which waste no MFMA rows (64 x
-    // 64 padded half): C4 0.362 -> 0.348 ms per iteration.  Not for N <= 64
-    // (LeNet conv1, N = 26: 0.199 -> 0.204 ms, the 128-wide B tile gathers
-    // mostly padding), profiles/r05_ab_split_thin32.txt
-    if constexpr (KB == 32) {
-      if (P.M <= 32 && P.N > 64) return launch_cfg<1, 4, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
-    }
-    // split-K grids: 64 x 64 tiles when an operand is that thin (conv weight gradients)
-    if (P.M <= 64 || P.N <= 64) return launch_cfg<2, 2, 1, 1, AM, BMODE, OM, KB>(P, gz, s);
-    return launch_cfg<2, 2, 2, 2, AM, BMODE, OM, KB>(P, gz, s);
-  }
   // thin M (CIFAR / LeNet convolutions, M = 20..32): a 32 x 128 tile wastes no
   // MFMA rows (64 x 64 would pad half of them)
   if constexpr (KB == 32) {
@@ -1358,6 +1367,15 @@ int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
   }
 }
 
+// IM2T instantiates the split form alone, so launch_tiles' other tiles are not built for it
+template <int AM, int BMODE, int OM, int KB>
+int launch(const Params& P, int gz, hipStream_t s, bool force_big, int pz = 0) {
+  if (force_big) return launch_split<AM, BMODE, OM, KB>(P, gz, s);
+  if constexpr (BMODE != IM2T) return launch_tiles<AM, BMODE, OM, KB>(P, gz, s, pz);
+  set_error("gemm: the gathered weight gradient has no unsplit form");
+  return RRAM_EUNSUPPORTED;
+}
+
 template <int AM, int BMODE, int OM>
 int launch2(Params P, int gz, hipStream_t s) {
   P.tiles_m = (P.M + g2::BM - 1) / g2::BM;
@@ -1396,8 +1414,10 @@ int conv_kb(int K) {
 
 // The instantiated (A mode, B mode, output mode) combinations of k_gemm: the
 // implicit-GEMM convolution forwards at 16-deep K-tiles (conv_kb), and every
-// combination at 32-deep ones.  dispatch() and rram_f32_kernel_list expand
-// the same lists.
+// combination at 32-deep ones (IM2T with launch_split's three tiles only).
+// dispatch() and rram_f32_kernel_list expand the same lists.
+// X(KC, CONVT, ...) stays although conv_fwd_core turns KC into KCU for every
+// table gather whose weights are below 2 GiB: larger weights still take it.
 #define RRAM_GEMM_LIST16(X)                                                                   \
   X(KC, CONV, OUT_NCHW) X(KCV, CONV, OUT_NCHW)                                                \
   X(KC, CONVT, OUT_NCHW) X(KCV, CONVT, OUT_NCHW) X(KCU, CONVT, OUT_NCHW)                      \
@@ -1449,25 +1469,20 @@ std::map<std::array<int, 11>, int2*>& conv_table_cache() {
   return cache;
 }
 
-const int2* conv_table(const ConvGeom& cv, int K, bool padded, bool wide, hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+// The device copy of the host table fill() builds, cached under key (key[0]:
+// the current HIP device, set here); nullptr when the device refuses it.
+template <class Fill>
+const int2* cached_table(std::array<int, 11> key, hipStream_t s, Fill fill) {
+  if (hipGetDevice(&key[0]) != hipSuccess) return nullptr;
   auto& cache = conv_table_cache();
-  const std::array<int, 11> key{dev, cv.C, cv.H, cv.W, cv.KH, cv.KW, cv.dh, cv.dw, padded ? 1 : 0, K, wide ? 1 : 0};
   std::lock_guard<std::mutex> g(conv_table_mutex());
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
-  const int len = (K + BK - 1) / BK * BK + 2 * BK;
-  std::vector<int2> h(len, int2{0, wide ? 63 : 31});  // the never-valid tap
-  for (int k = 0; k < K; ++k) {
-    const int c = k / (cv.KH * cv.KW), r = k % (cv.KH * cv.KW);
-    const int kh = r / cv.KW, kw = r % cv.KW;
-    h[k].x = 4 * (c * cv.H * cv.W + kh * cv.dh * cv.W + kw * cv.dw);
-    h[k].y = padded ? r : 0;
-  }
+  const std::vector<int2> h = fill();
+  const size_t bytes = h.size() * sizeof(int2);
   int2* d = nullptr;
-  if (hipMalloc(&d, len * sizeof(int2)) != hipSuccess) return nullptr;
-  if (hipMemcpyAsync(d, h.data(), len * sizeof(int2), hipMemcpyHostToDevice, s) != hipSuccess ||
+  if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+  if (hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) {
     (void)hipFree(d);
     return nullptr;
@@ -1476,36 +1491,39 @@ const int2* conv_table(const ConvGeom& cv, int K, bool padded, bool wide, hipStr
   return d;
 }
 
+// len entries of pad, the first K of them {input offset of reduction index
+// k = (c, kh, kw) in bytes, y_of(kh, kw, kh*KW + kw)}
+template <class Y>
+std::vector<int2> gather_rows(const ConvGeom& cv, int K, int len, int2 pad, Y y_of) {
+  std::vector<int2> h(len, pad);
+  for (int k = 0; k < K; ++k) {
+    const int c = k / (cv.KH * cv.KW), r = k % (cv.KH * cv.KW);
+    const int kh = r / cv.KW, kw = r % cv.KW;
+    h[k] = int2{4 * (c * cv.H * cv.W + kh * cv.dh * cv.W + kw * cv.dw), y_of(kh, kw, r)};
+  }
+  return h;
+}
+
+const int2* conv_table(const ConvGeom& cv, int K, bool padded, bool wide, hipStream_t s) {
+  const int len = (K + BK - 1) / BK * BK + 2 * BK;
+  return cached_table({0, cv.C, cv.H, cv.W, cv.KH, cv.KW, cv.dh, cv.dw, padded ? 1 : 0, K, wide ? 1 : 0}, s, [&] {
+    return gather_rows(cv, K, len, int2{0, wide ? 63 : 31},  // the never-valid tap
+                       [&](int, int, int tap) { return padded ? tap : 0; });
+  });
+}
+
 // Row table of the IM2T loader (cached with the CONVT tables): entry n < K
 // holds row n = (c, kh, kw) of the column matrix as {4 (c H W + kh dh W +
 // kw dw), kh dh | kw dw << 16}; entry K the ones row {0, -1} when `ones`;
 // the rest (tile padding) {0, 0x7FFF7FFF}, never inside the image.
 const int2* im2t_table(const ConvGeom& cv, int K, bool ones, int rows_pad, hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  auto& cache = conv_table_cache();
   const int len = (K + 1 + rows_pad - 1) / rows_pad * rows_pad + rows_pad;
-  const std::array<int, 11> key{dev, cv.C, cv.H, cv.W, cv.KH, cv.KW, cv.dh, cv.dw, len, K, ones ? 3 : 2};
-  std::lock_guard<std::mutex> g(conv_table_mutex());
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  std::vector<int2> h(len, int2{0, 0x7FFF7FFF});
-  for (int k = 0; k < K; ++k) {
-    const int c = k / (cv.KH * cv.KW), r = k % (cv.KH * cv.KW);
-    const int kh = r / cv.KW, kw = r % cv.KW;
-    h[k].x = 4 * (c * cv.H * cv.W + kh * cv.dh * cv.W + kw * cv.dw);
-    h[k].y = (kh * cv.dh) | ((kw * cv.dw) << 16);
-  }
-  if (ones) h[K] = int2{0, -1};
-  int2* d = nullptr;
-  if (hipMalloc(&d, len * sizeof(int2)) != hipSuccess) return nullptr;
-  if (hipMemcpyAsync(d, h.data(), len * sizeof(int2), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    (void)hipFree(d);
-    return nullptr;
-  }
-  cache[key] = d;
-  return d;
+  return cached_table({0, cv.C, cv.H, cv.W, cv.KH, cv.KW, cv.dh, cv.dw, len, K, ones ? 3 : 2}, s, [&] {
+    std::vector<int2> h = gather_rows(cv, K, len, int2{0, 0x7FFF7FFF},
+                                      [&](int kh, int kw, int) { return (kh * cv.dh) | ((kw * cv.dw) << 16); });
+    if (ones) h[K] = int2{0, -1};
+    return h;
+  });
 }
 
 }  // namespace
@@ -1539,6 +1557,47 @@ int gemm_x6_nt(int M, int N, int K, float alpha, const float* A, int lda, const 
                hipStream_t s, const void* a_rows = nullptr, char* y_rows = nullptr, int y_bmc = 0);
 void gemm_split_plan(int M, int N, int K, bool have_ws, size_t ws_bytes, int& split_out, int& chunk_out);
 
+// K cut into `split` chunks of `chunk` elements, a multiple of the K-tile
+// `unit`: ceil(K / want) rounded up to the unit, then as many chunks as K needs
+struct SplitK {
+  int split, chunk;
+};
+SplitK split_chunks(int K, int want, int unit) {
+  const int chunk = ((K + want - 1) / want + unit - 1) / unit * unit;
+  return {(K + chunk - 1) / chunk, chunk};
+}
+// the largest split <= want (>= min) whose [split][M][N] fp32 partials fit bytes, else min
+int fit_split(int want, int min, int M, int N, size_t bytes) {
+  while (want > min && (size_t)want * M * N * sizeof(float) > bytes) --want;
+  return want;
+}
+
+// The row-major product P describes (its views, epilogue, M, N, K and group
+// strides) on the fp32 kernel: plan the split, dispatch, reduce.  G = 0: one
+// product (gemm_core); G >= 1: G groups in the grid's z (gemm_groups_core).
+int dense_product(Params P, int am, int bm, int G, void* ws, size_t ws_bytes, hipStream_t s) {
+  const int gz = std::max(G, 1);
+  P.split = 1;
+  P.k_chunk = P.K;
+  int split = 1, chunk = P.K;
+  gemm_split_plan(P.M, P.N, P.K, ws != nullptr, ws_bytes, split, chunk);
+  if (split == 1) return dispatch(am, bm, OUT_ROWMAJOR, P, gz, s, false, 1);  // z = group (the conv-group path)
+  P.split = split;
+  P.k_chunk = chunk;
+  P.ws = static_cast<float*>(ws);
+  P.zgroups = G;
+  const int rc = dispatch(am, bm, OUT_ROWMAJOR, P, gz * split, s, true);
+  if (rc) return rc;
+  if (plan_note(G ? "reduce_groups" : "reduce")) return RRAM_OK;
+  const dim3 grid(stream_blocks((int64_t)gz * P.M * P.N));
+  if (G)
+    hipLaunchKernelGGL(k_splitk_reduce_groups, grid, dim3(256), 0, s, P.ws, split, P.M, P.N, P.e, G, P.grp_c,
+                       P.grp_bias);
+  else
+    hipLaunchKernelGGL(k_splitk_reduce, grid, dim3(256), 0, s, P.ws, split, P.M, P.N, P.e);
+  return launch_status("gemm splitk reduce");
+}
+
 int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const float* A, int lda,
               const float* B, int ldb, float beta, float* C, int ldc, const float* bias,
               int bias_mode, int relu, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -1560,27 +1619,12 @@ int gemm_core(int trans_a, int trans_b, int M, int N, int K, float alpha, const 
   P.M = M;
   P.N = N;
   P.K = K;
-  P.split = 1;
-  P.k_chunk = K;
   // op(A)(m,k) = trans_a ? A[k*lda+m] : A[m*lda+k]; op(B)(k,n) = trans_b ? B[n*ldb+k] : B[k*ldb+n]
   int am = trans_a ? RC : KC;
   int bm = trans_b ? KC : RC;
   if (am == KC && vec_ok(A, lda, K)) am = KCV;
   if (bm == KC && vec_ok(B, ldb, K)) bm = KCV;
-  int split = 1, chunk = K;
-  gemm_split_plan(M, N, K, ws != nullptr, ws_bytes, split, chunk);
-  if (split > 1) {
-    P.split = split;
-    P.k_chunk = chunk;
-    P.ws = static_cast<float*>(ws);
-    int rc = dispatch(am, bm, OUT_ROWMAJOR, P, split, s, true);
-    if (rc) return rc;
-    if (plan_note("reduce")) return RRAM_OK;
-    hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s,
-                       P.ws, split, M, N, P.e);
-    return launch_status("gemm splitk reduce");
-  }
-  return dispatch(am, bm, OUT_ROWMAJOR, P, 1, s);
+  return dense_product(P, am, bm, 0, ws, ws_bytes, s);
 }
 
 // The split-K plan of gemm_core's fp32 kernel for an [M][N] output over K:
@@ -1603,16 +1647,11 @@ void gemm_split_plan(int M, int N, int K, bool have_ws, size_t ws_bytes, int& sp
     split = static_cast<int>(target / (tiles > 0 ? tiles : 1));
     if (split > target / 16) split = target / 16;
     while (split > 1 && (K / split) < std::min(256, mink / 2)) --split;
-    while (split > 1 && (size_t)split * M * N * sizeof(float) > ws_bytes) --split;
+    split = fit_split(split, 1, M, N, ws_bytes);
   }
-  int chunk = K;
-  if (split > 1) {
-    chunk = (K + split - 1) / split;
-    chunk = (chunk + BK - 1) / BK * BK;
-    split = (K + chunk - 1) / chunk;
-  }
-  split_out = split;
-  chunk_out = split > 1 ? chunk : K;
+  const SplitK sk = split > 1 ? split_chunks(K, split, BK) : SplitK{1, K};
+  split_out = sk.split;
+  chunk_out = sk.split > 1 ? sk.chunk : K;
 }
 
 // The operand modes gemm_core picks for C = A . op(B) with row-major A [M][K]
@@ -1664,28 +1703,11 @@ int gemm_groups_core(int G, int trans_b, int M, int N, int K, const float* A, in
   P.M = M;
   P.N = N;
   P.K = K;
-  P.split = 1;
-  P.k_chunk = K;
   P.grp_a = grp_a;
   P.grp_b = grp_b;
   P.grp_c = grp_c;
   P.grp_bias = grp_bias;
-  int split = 1, chunk = K;
-  gemm_split_plan(M, N, K, ws != nullptr, ws_bytes, split, chunk);
-  if (split > 1) {
-    P.split = split;
-    P.k_chunk = chunk;
-    P.ws = static_cast<float*>(ws);
-    P.zgroups = G;
-    int rc = dispatch(am, bm, OUT_ROWMAJOR, P, G * split, s, true, split);
-    if (rc) return rc;
-    if (plan_note("reduce_groups")) return 1;
-    hipLaunchKernelGGL(k_splitk_reduce_groups, dim3(stream_blocks((int64_t)G * M * N)), dim3(256), 0, s, P.ws, split, M,
-                       N, P.e, G, grp_c, grp_bias);
-    rc = launch_status("gemm groups splitk reduce");
-    return rc ? rc : 1;
-  }
-  const int rc = dispatch(am, bm, OUT_ROWMAJOR, P, G, s, false, 1);  // z = group (the conv-group path)
+  const int rc = dense_product(P, am, bm, G, ws, ws_bytes, s);
   return rc ? rc : 1;
 }
 
@@ -1883,6 +1905,31 @@ int conv_fwd_split(const rram_conv_desc* d, int M, int N, int K) {
   return std::min(split, 16);
 }
 
+// One group's gather geometry: every ConvGeom field the descriptor alone
+// decides.  tbl, taps and in_bytes are the caller's.
+ConvGeom make_conv_geom(const rram_conv_desc* d) {
+  ConvGeom cv{};
+  cv.C = d->channels / d->group;
+  cv.H = d->height;
+  cv.W = d->width;
+  cv.KH = d->kernel_h;
+  cv.KW = d->kernel_w;
+  cv.ph = d->pad_h;
+  cv.pw = d->pad_w;
+  cv.sh = d->stride_h;
+  cv.sw = d->stride_w;
+  cv.dh = d->dilation_h;
+  cv.dw = d->dilation_w;
+  cv.Ho = d->out_h;
+  cv.Wo = d->out_w;
+  cv.khkw = make_fastdiv(d->kernel_h * d->kernel_w);
+  cv.kw_div = make_fastdiv(d->kernel_w);
+  cv.howo = make_fastdiv(d->out_h * d->out_w);
+  cv.wo_div = make_fastdiv(d->out_w);
+  cv.chw = (int64_t)d->channels * d->height * d->width;
+  return cv;
+}
+
 int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const float* bias,
                   float* y, int relu, hipStream_t s, int64_t y_img) {
   {
@@ -1904,24 +1951,7 @@ int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const
   P.a = make_view(w, K, cout_g, K);
   P.b = make_view(x, 0, P.N, K);
   ConvGeom& cv = P.cv;
-  cv.C = cin_g;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = d->kernel_h;
-  cv.KW = d->kernel_w;
-  cv.ph = d->pad_h;
-  cv.pw = d->pad_w;
-  cv.sh = d->stride_h;
-  cv.sw = d->stride_w;
-  cv.dh = d->dilation_h;
-  cv.dw = d->dilation_w;
-  cv.Ho = d->out_h;
-  cv.Wo = d->out_w;
-  cv.khkw = make_fastdiv(d->kernel_h * d->kernel_w);
-  cv.kw_div = make_fastdiv(d->kernel_w);
-  cv.howo = make_fastdiv(HoWo);
-  cv.wo_div = make_fastdiv(d->out_w);
-  cv.chw = (int64_t)d->channels * d->height * d->width;
+  cv = make_conv_geom(d);
   RRAM_REQUIRE((int64_t)d->num * cv.chw * 4 < (1ll << 31), "conv2d_fwd: input must be < 2 GiB (32-bit buffer offsets)");
   cv.in_bytes = static_cast<int>((int64_t)d->num * cv.chw * 4);
   P.e = make_epi(y, HoWo, 1.0f, 0.0f, bias, RRAM_BIAS_ROW, relu);
@@ -1959,19 +1989,17 @@ int conv_fwd_core(const rram_conv_desc* d, const float* x, const float* w, const
   {
     const int split = conv_fwd_split(d, P.M, P.N, K);
     if (split > 1) {
-      const int kb = conv_kb(K);
-      const int kc = ((K + split - 1) / split + kb - 1) / kb * kb;
-      const int sp = (K + kc - 1) / kc;
-      float* ws = planning() ? nullptr : stream_buffer(1, (size_t)sp * P.M * P.N, s);
+      const SplitK sk = split_chunks(K, split, conv_kb(K));
+      float* ws = planning() ? nullptr : stream_buffer(1, (size_t)sk.split * P.M * P.N, s);
       RRAM_REQUIRE(ws != nullptr || planning(), "conv2d_fwd: split-K buffer allocation failed");
-      P.split = sp;
-      P.k_chunk = kc;
+      P.split = sk.split;
+      P.k_chunk = sk.chunk;
       P.ws = ws;
-      int rc = dispatch(amode, bmode, OUT_NCHW, P, sp, s);
+      int rc = dispatch(amode, bmode, OUT_NCHW, P, sk.split, s);
       if (rc) return rc;
       if (plan_note("reduce_nchw")) return RRAM_OK;
-      hipLaunchKernelGGL(k_splitk_reduce_nchw, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, ws, sp, P.M,
-                         P.N, P.e);
+      hipLaunchKernelGGL(k_splitk_reduce_nchw, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, ws, sk.split,
+                         P.M, P.N, P.e);
       return launch_status("conv fwd split-K reduce");
     }
   }
@@ -2002,18 +2030,8 @@ int bwd_weight_split(int M, int N, int64_t K) {
   return static_cast<int>(sp < 1 ? 1 : sp);
 }
 
-// dW_g[co][k] += sum_p dY_g[co][p] col_g[k][p]   (col: [Cin*kh*kw][ldcol]);
-// part (nullable): part_bytes of split-K partials (see bwd_weight_split)
-// db (nullable; ungrouped only, part required): the bias gradient as one more
-// GEMM column against the ones row im2col_core wrote after the K column rows,
-// always split (>= 2), the reduce routing column K to db
-// The weight gradient with the column matrix gathered inside the GEMM (IM2T,
-// no im2col pass and no column buffer): dW_g[co][k] += sum_p dY_g[co][p]
-// x_g[k, p] over all d->num images; db (group 1 only) as the ones row's
-// column of the same split GEMM.  part: the split-K partials (required:
-// these are long-K GEMMs); 0 when not covered (the caller falls back to the
-// column path), < 0 on error.  The same K-tiles, split and element values as
-// the im2col + KC path, so the same bits.
+// Whether conv_bwd_weight_im2t covers d with part_bytes of partials (else the
+// caller takes the column path)
 bool conv_bwd_weight_im2t_ok(const rram_conv_desc* d, size_t part_bytes) {
   const int g = d->group;
   const int cout_g = d->num_output / g, K = d->channels / g * d->kernel_h * d->kernel_w;
@@ -2023,152 +2041,99 @@ bool conv_bwd_weight_im2t_ok(const rram_conv_desc* d, size_t part_bytes) {
          (d->kernel_h - 1) * d->dilation_h < 32768 && (d->kernel_w - 1) * d->dilation_w < 32768 &&
          part_bytes >= 2 * (size_t)cout_g * (K + 1) * sizeof(float);
 }
+
+// dst += the sum of P's split-K partials: dw [P.M][K] and, when db, column K
+// of the P.N = K + 1 to db.  One wave per output from reduce_by_wave(split)
+// on, else the sequential sums in split order.
+int launch_weight_reduce(const Params& P, int split, int K, float* db, hipStream_t s) {
+  const bool wave = reduce_by_wave(split);
+  if (plan_note(wave ? "reduce_wave" : db ? "reduce_dwdb" : "reduce")) return RRAM_OK;
+  const int64_t outs = (int64_t)P.M * P.N;
+  if (wave)
+    hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>((outs + 3) / 4)), dim3(256), 0, s, P.ws, split,
+                       P.M, K, P.N, P.e.C, db);
+  else if (db)
+    hipLaunchKernelGGL(k_splitk_reduce_dwdb, dim3(stream_blocks(outs)), dim3(256), 0, s, P.ws, split, P.M, K, P.e.C, db);
+  else
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks(outs)), dim3(256), 0, s, P.ws, split, P.M, P.N, P.e);
+  return launch_status("conv bwd weight split-K reduce");
+}
+
+// Group gi's weight-gradient product dW_g[co][k] += sum_p dY_g[co][p] B[k][p]
+// over P.K positions: P brings the B operand (mode bm: the column matrix, or
+// IM2T's gather with P.cv), N = K (+ 1: db's ones row) and P.K.  Split as
+// bwd_weight_split asks, cut to what part_bytes holds but not below
+// min_split, and reduced into dw (beta = 1) in a fixed order; unsplit (the
+// column path without partials) straight into dw.
+int bwd_weight_gemm(const rram_conv_desc* d, int gi, const float* dy, float* dw, float* db, Params P, int bm,
+                    int min_split, void* part, size_t part_bytes, hipStream_t s) {
+  const int cout_g = d->num_output / d->group;
+  const int K = d->channels / d->group * d->kernel_h * d->kernel_w;
+  const int HoWo = d->out_h * d->out_w;
+  P.M = cout_g;
+  P.split = 1;
+  P.k_chunk = P.K;
+  P.a = make_view(dy + (int64_t)gi * cout_g * HoWo, HoWo, cout_g, P.K);
+  P.a.img = (int64_t)d->num_output * HoWo;
+  P.a.hw = make_fastdiv(HoWo);
+  P.e = make_epi(dw + (int64_t)gi * cout_g * K, K, 1.0f, 1.0f, nullptr, 0, 0);
+  const int want = fit_split(part ? std::max(min_split, bwd_weight_split(P.M, P.N, P.K)) : 1, min_split, P.M, P.N,
+                             part_bytes);
+  if (want <= 1) return dispatch(NCHW, bm, OUT_ROWMAJOR, P, 1, s);
+  const SplitK sk = split_chunks(P.K, want, BK);
+  RRAM_REQUIRE(sk.split >= min_split && (size_t)sk.split * P.M * P.N * sizeof(float) <= part_bytes,
+               "conv bwd weight: the split-K partials do not fit (>= %d K splits needed)", min_split);
+  P.split = sk.split;
+  P.k_chunk = sk.chunk;
+  P.ws = static_cast<float*>(part);
+  const int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, sk.split, s, true);
+  return rc ? rc : launch_weight_reduce(P, sk.split, K, db, s);
+}
+
+// The weight gradient with the column matrix gathered inside the GEMM (IM2T,
+// no im2col pass and no column buffer) over all d->num images; db (group 1
+// only) as the ones row's column of the same split GEMM.  part: the split-K
+// partials (required: these are long-K GEMMs, always split >= 2).  The same
+// K-tiles, split and element values as the im2col + KC path, so the same bits.
 int conv_bwd_weight_im2t(const rram_conv_desc* d, const float* x, const float* dy, float* dw, float* db, void* part,
                          size_t part_bytes, hipStream_t s) {
   const int g = d->group;
-  const int cin_g = d->channels / g, cout_g = d->num_output / g;
-  const int K = cin_g * d->kernel_h * d->kernel_w;
-  const int HoWo = d->out_h * d->out_w;
-  const int64_t P_all = (int64_t)d->num * HoWo;
+  const int K = d->channels / g * d->kernel_h * d->kernel_w;
+  const int64_t grp_x = (int64_t)d->channels / g * d->height * d->width;
   const int64_t in_elems = (int64_t)d->num * d->channels * d->height * d->width;
   RRAM_REQUIRE(part != nullptr && conv_bwd_weight_im2t_ok(d, part_bytes) && (db == nullptr || g == 1),
                "conv bwd weight (gathered): shape or workspace not covered");
-  ConvGeom cv{};
-  cv.C = cin_g;
-  cv.H = d->height;
-  cv.W = d->width;
-  cv.KH = d->kernel_h;
-  cv.KW = d->kernel_w;
-  cv.ph = d->pad_h;
-  cv.pw = d->pad_w;
-  cv.sh = d->stride_h;
-  cv.sw = d->stride_w;
-  cv.dh = d->dilation_h;
-  cv.dw = d->dilation_w;
-  cv.Ho = d->out_h;
-  cv.Wo = d->out_w;
-  cv.howo = make_fastdiv(HoWo);
-  cv.wo_div = make_fastdiv(d->out_w);
-  cv.chw = (int64_t)d->channels * d->height * d->width;
-  if (!planning()) cv.tbl = im2t_table(cv, K, db != nullptr, 256, s);
-  RRAM_REQUIRE(cv.tbl != nullptr || planning(), "conv bwd weight: gather table allocation failed");
-  const int N = K + (db ? 1 : 0);
+  Params P{};
+  P.cv = make_conv_geom(d);
+  if (!planning()) P.cv.tbl = im2t_table(P.cv, K, db != nullptr, 256, s);
+  RRAM_REQUIRE(P.cv.tbl != nullptr || planning(), "conv bwd weight: gather table allocation failed");
+  P.N = K + (db ? 1 : 0);
+  P.K = static_cast<int>((int64_t)d->num * d->out_h * d->out_w);
   for (int gi = 0; gi < g; ++gi) {
-    Params P{};
-    P.M = cout_g;
-    P.N = N;
-    P.K = static_cast<int>(P_all);
-    P.a = make_view(dy + (int64_t)gi * cout_g * HoWo, HoWo, cout_g, P.K);
-    P.a.img = (int64_t)d->num_output * HoWo;
-    P.a.hw = make_fastdiv(HoWo);
-    P.b = make_view(x + (int64_t)gi * cin_g * d->height * d->width, 0, N, P.K);
-    P.cv = cv;
-    P.cv.in_bytes = static_cast<int>((in_elems - (int64_t)gi * cin_g * d->height * d->width) * 4);
-    P.e = make_epi(dw + (int64_t)gi * cout_g * K, K, 1.0f, 1.0f, nullptr, 0, 0);
-    int split = std::max(2, bwd_weight_split(P.M, P.N, P.K));
-    while (split > 2 && (size_t)split * P.M * P.N * sizeof(float) > part_bytes) --split;
-    int chunk = (P.K + split - 1) / split;
-    chunk = (chunk + BK - 1) / BK * BK;
-    split = (P.K + chunk - 1) / chunk;
-    RRAM_REQUIRE(split >= 2 && (size_t)split * P.M * P.N * sizeof(float) <= part_bytes,
-                 "conv bwd weight (gathered): split-K partials do not fit");
-    P.split = split;
-    P.k_chunk = chunk;
-    P.ws = static_cast<float*>(part);
-    int rc = dispatch(NCHW, IM2T, OUT_ROWMAJOR, P, split, s, true);
-    if (rc) return rc;
-    if (plan_note(reduce_by_wave(split) ? "reduce_wave" : db ? "reduce_dwdb" : "reduce")) continue;
-    if (reduce_by_wave(split))
-      hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256), 0,
-                         s, P.ws, split, P.M, K, P.N, P.e.C, db);
-    else if (db)
-      hipLaunchKernelGGL(k_splitk_reduce_dwdb, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, P.ws, split,
-                         P.M, K, P.e.C, db);
-    else
-      hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, P.ws, split,
-                         P.M, P.N, P.e);
-    rc = launch_status("conv bwd weight (gathered) split-K reduce");
+    P.b = make_view(x + gi * grp_x, 0, P.N, P.K);
+    P.cv.in_bytes = static_cast<int>((in_elems - gi * grp_x) * 4);
+    const int rc = bwd_weight_gemm(d, gi, dy, dw, db, P, IM2T, 2, part, part_bytes, s);
     if (rc) return rc;
   }
   return RRAM_OK;
 }
 
+// The column path: col [Cin*kh*kw (+ 1)][ldcol] as im2col_core wrote it for
+// nimg images, group gi's rows from gi * K on.  part (nullable): part_bytes of
+// split-K partials.  db (nullable; ungrouped only, part required): the bias
+// gradient as one more GEMM column against the ones row after the K column rows.
 int conv_bwd_weight_core(const rram_conv_desc* d, int nimg, const float* dy, const float* col,
                          int64_t ldcol, float* dw, void* part, size_t part_bytes, hipStream_t s, float* db) {
   const int g = d->group;
-  const int cin_g = d->channels / g, cout_g = d->num_output / g;
-  const int K = cin_g * d->kernel_h * d->kernel_w;
-  const int HoWo = d->out_h * d->out_w;
+  const int K = d->channels / g * d->kernel_h * d->kernel_w;
   RRAM_REQUIRE(db == nullptr || (g == 1 && part != nullptr), "conv bwd weight: folded bias needs group 1 + partials");
-  if (db) {
-    Params P{};
-    P.M = cout_g;
-    P.N = K + 1;
-    P.K = nimg * HoWo;
-    P.a = make_view(dy, HoWo, cout_g, P.K);
-    P.a.img = (int64_t)d->num_output * HoWo;
-    P.a.hw = make_fastdiv(HoWo);
-    P.b = make_view(col, ldcol, K + 1, P.K);
-    P.e = make_epi(dw, K, 1.0f, 1.0f, nullptr, 0, 0);
+  Params P{};
+  P.N = K + (db ? 1 : 0);
+  P.K = nimg * d->out_h * d->out_w;
+  for (int gi = 0; gi < g; ++gi) {  // (db: g = 1, always split, the reduce routing column K to db)
+    P.b = make_view(col + (int64_t)gi * K * ldcol, ldcol, P.N, P.K);
     const int bm = vec_ok(P.b.p, ldcol, P.K) ? KCV : KC;
-    int split = std::max(2, bwd_weight_split(P.M, P.N, P.K));
-    while (split > 2 && (size_t)split * P.M * P.N * sizeof(float) > part_bytes) --split;
-    int chunk = (P.K + split - 1) / split;
-    chunk = (chunk + BK - 1) / BK * BK;
-    split = (P.K + chunk - 1) / chunk;
-    RRAM_REQUIRE(split >= 2 && (size_t)split * P.M * P.N * sizeof(float) <= part_bytes,
-                 "conv bwd weight: folded bias needs >= 2 K splits");
-    P.split = split;
-    P.k_chunk = chunk;
-    P.ws = static_cast<float*>(part);
-    int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, split, s, true);
-    if (rc) return rc;
-    if (plan_note(reduce_by_wave(split) ? "reduce_wave" : "reduce_dwdb")) return RRAM_OK;
-    if (reduce_by_wave(split))
-      hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256), 0,
-                         s, P.ws, split, P.M, K, P.N, dw, db);
-    else
-      hipLaunchKernelGGL(k_splitk_reduce_dwdb, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, P.ws, split,
-                         P.M, K, dw, db);
-    return launch_status("conv bwd weight + bias split-K reduce");
-  }
-  for (int gi = 0; gi < g; ++gi) {
-    Params P{};
-    P.M = cout_g;
-    P.N = K;
-    P.K = nimg * HoWo;
-    P.split = 1;
-    P.k_chunk = P.K;
-    P.a = make_view(dy + (int64_t)gi * cout_g * HoWo, HoWo, cout_g, P.K);
-    P.a.img = (int64_t)d->num_output * HoWo;
-    P.a.hw = make_fastdiv(HoWo);
-    P.b = make_view(col + (int64_t)gi * K * ldcol, ldcol, K, P.K);
-    P.e = make_epi(dw + (int64_t)gi * cout_g * K, K, 1.0f, 1.0f, nullptr, 0, 0);
-    const int bm = vec_ok(P.b.p, ldcol, P.K) ? KCV : KC;
-    int split = part ? bwd_weight_split(P.M, P.N, P.K) : 1;
-    while (split > 1 && (size_t)split * P.M * P.N * sizeof(float) > part_bytes) --split;
-    if (split > 1) {
-      int chunk = (P.K + split - 1) / split;
-      chunk = (chunk + BK - 1) / BK * BK;
-      split = (P.K + chunk - 1) / chunk;
-      P.split = split;
-      P.k_chunk = chunk;
-      P.ws = static_cast<float*>(part);
-      int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, split, s, true);
-      if (rc) return rc;
-      // dw += sum of the partials (beta = 1), fixed summation order
-      if (plan_note(reduce_by_wave(split) ? "reduce_wave" : "reduce")) continue;
-      if (reduce_by_wave(split))  // (dw of group gi: P.e.C)
-        hipLaunchKernelGGL(k_splitk_reduce_wave, dim3(static_cast<unsigned>(((int64_t)P.M * P.N + 3) / 4)), dim3(256),
-                           0, s, P.ws, split, P.M, P.N, P.N, P.e.C, nullptr);
-      else
-        hipLaunchKernelGGL(k_splitk_reduce, dim3(stream_blocks((int64_t)P.M * P.N)), dim3(256), 0, s, P.ws, split,
-                           P.M, P.N, P.e);
-      rc = launch_status("conv bwd weight split-K reduce");
-      if (rc) return rc;
-      continue;
-    }
-    const int rc = dispatch(NCHW, bm, OUT_ROWMAJOR, P, 1, s);
+    const int rc = bwd_weight_gemm(d, gi, dy, dw, db, P, bm, db ? 2 : 1, part, part_bytes, s);
     if (rc) return rc;
   }
   return RRAM_OK;
@@ -2259,7 +2224,8 @@ std::string f32_kernel_list() {
   RRAM_GEMM_LIST16(RRAM_X)
 #undef RRAM_X
 #define RRAM_X(A_, B_, O_) \
-  for (const auto& t : kTiles32) out += gemm_id(A_, B_, O_, 32, t[0], t[1], 0) + "\n";
+  for (const auto& t : kTiles32)                 \
+    if (B_ != IM2T || split_tile(t[0], t[1])) out += gemm_id(A_, B_, O_, 32, t[0], t[1], 0) + "\n";
   RRAM_GEMM_LIST32(RRAM_X)
 #undef RRAM_X
   out += "gemm2<KCV,KCV,ROWMAJOR,3>\n";

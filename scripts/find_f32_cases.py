@@ -7,6 +7,7 @@ listed id no case runs.  Host only (no GPU).
 
     python scripts/find_f32_cases.py            # report
     python scripts/find_f32_cases.py --write    # rewrite tests/_f32_cases.py
+    python scripts/find_f32_cases.py --dump F   # every planner answer per searched case (to diff two builds)
 """
 import itertools
 import pprint
@@ -74,6 +75,40 @@ def conv():
                         yield dict(entry="conv_bwd", **base, dw=dw, db=db, dx=dx, ws=ws, wflip=wflip)
 
 
+def ws_sweep():
+    """conv_bwd across every edge of the image-chunk plan: per group count the
+    F32_CASES weight-gradient case with the most output positions, at batch 1,
+    2 and 8, with the workspace of each chunk size 1..batch, those +-4 and
+    +-256 bytes (the partials' 256-byte rounding) and halved."""
+    for g in (1, 2):
+        pick = max((c for c in F.F32_CASES if c["entry"] == "conv_bwd" and c["dw"] and c["g"] == g),
+                   key=lambda c: F.conv_desc(c).out_h * F.conv_desc(c).out_w)
+        for n in (1, 2, 8):
+            base = dict({k: v for k, v in pick.items() if k != "ids"}, x=(n,) + tuple(pick["x"][1:]), wflip=False)
+            d = F.conv_desc(base)
+            full = [ops.conv2d_bwd_workspace(d, m) for m in range(1, n + 1)]
+            for ws in sorted({w + e for w in full for e in (0, -4, 4, -256, 256)} | {w // 2 for w in full}):
+                for dw, db, dx in ((1, 0, 0), (1, 1, 0), (1, 1, 1), (0, 0, 1)):
+                    if ws >= 0:
+                        yield dict(base, dw=dw, db=db, dx=dx, ws=ws)
+
+
+def dump(path):
+    """One line per searched case with the planner's whole answer (or its
+    error text): two builds whose files are equal plan every case alike."""
+    n = 0
+    with open(path, "w") as f:
+        for cs in itertools.chain(dense(), ip(), conv(), F.F32_CASES, ws_sweep()):
+            cs = {k: v for k, v in cs.items() if k != "ids"}
+            try:
+                ans = " | ".join(F.ids_of(cs))
+            except Kmod.RramError as e:
+                ans = f"RramError: {e}"
+            f.write(f"{cs!r}\t{ans}\n")
+            n += 1
+    print(f"# {n} cases dumped to {path}", file=sys.stderr)
+
+
 def _aux(c, prefix):
     return any(ln.startswith(prefix) for ln in c["ids"])
 
@@ -97,6 +132,8 @@ FORMS = {
 
 
 def main():
+    if "--dump" in sys.argv:
+        return dump(sys.argv[sys.argv.index("--dump") + 1])
     listed = ops.f32_kernel_list()
     best, over, rag, forms = {}, {}, {}, {}
     n = 0
@@ -190,10 +227,6 @@ for _kb, _tiles in ((16, ("64x64", "64x128", "128x128", "192x128", "128x256")),
         NEVER[f"gemm<KC,CONVT,NCHW,{_kb};{_t}>"] = (
             "not found in the search box: SEARCH_BOX['conv'] (conv_fwd_core turns KC into KCU for every table gather, "
             "amode == KC && bmode == CONVT, whose weights are below 2 GiB; the box's weights stay below 64 MiB)")
-for _t in ("64x128", "96x128", "192x128"):
-    NEVER[f"gemm<NCHW,IM2T,ROWMAJOR,32;{_t}>"] = (
-        "never launched: the gathered weight gradient is always split (conv_bwd_weight_im2t: split >= 2) and a "
-        "split grid takes 32x128, 64x64 or 128x128 (launch<>, force_big)")
 
 if __name__ == "__main__":
     main()

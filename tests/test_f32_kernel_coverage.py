@@ -29,12 +29,14 @@ def test_case_selects_its_kernels(i):
 
 
 def test_kernel_list_is_the_instantiated_set():
-    """k_gemm: 20 operand-mode lines x 6 tiles at 32-deep K-tiles and 7 x 5 at
-    16-deep ones; k_gemm2; 10 fp32 patch forms; the weight pack, 2 GEMVs, 3
-    column-matrix kernels and 5 split-K reduces."""
+    """k_gemm: 19 operand-mode lines x 6 tiles and IM2T's 3 split-grid tiles at
+    32-deep K-tiles and 7 x 5 at 16-deep ones; k_gemm2; 10 fp32 patch forms;
+    the weight pack, 2 GEMVs, 3 column-matrix kernels and 5 split-K reduces."""
     from rramsim import ops
     ids = ops.f32_kernel_list()
-    assert len(ids) == len(set(ids)) == 20 * 6 + 7 * 5 + 1 + 10 + 1 + 2 + 3 + 5
+    assert len(ids) == len(set(ids)) == 19 * 6 + 3 + 7 * 5 + 1 + 10 + 1 + 2 + 3 + 5
+    im2t = [f"gemm<NCHW,IM2T,ROWMAJOR,32;{t}>" for t in ("32x128", "64x64", "128x128")]
+    assert [k for k in ids if ",IM2T," in k] == im2t       # the split-grid tiles alone
     for k in ids:
         assert re.fullmatch(r"gemm<[A-Z0-9]+,[A-Z0-9]+,(ROWMAJOR|NCHW),(16|32);\d+x\d+>|gemm2<KCV,KCV,ROWMAJOR,3>|"
                             r"patch_f32<\d,\d,\d,\d>|patch_pack|gemv|gemv_groups|im2col4?|col2im|"
