@@ -555,8 +555,12 @@ int rram_pack_octets(const float* x, void* oct, int num, int channels, int heigh
  *                      v_mfma_f32_32x32x16_bf16 (fp32-accurate products, ~2x
  *                      the fp32 matrix-core rate).  Used by the stride-1
  *                      3x3 / 5x5 convolution forward and the InnerProduct /
- *                      NoTrans x Trans GEMM forward (rram_ip_fwd); every
- *                      other contraction stays on RRAM_ENGINE_F32.
+ *                      NoTrans x Trans GEMM forward (rram_ip_fwd), by the
+ *                      stride-1 data gradient (a forward convolution with
+ *                      the flipped kernel) and, opt-in, by the stride-1
+ *                      3x3 / 5x5 weight gradient (rram_set_bwd_weight_engine
+ *                      below); every other contraction stays on
+ *                      RRAM_ENGINE_F32.
  * The initial value comes from RRAM_X6 (0 = F32).  Returns the previous
  * engine, or RRAM_EINVAL for an unknown one. */
 enum { RRAM_ENGINE_F32 = 0, RRAM_ENGINE_BF16X6 = 1 };
@@ -566,9 +570,29 @@ int rram_get_f32_engine(void);
  * operands, workspace of ws_bytes) would use for this shape right now. */
 int rram_f32_engine_for_conv(const rram_conv_desc* d);
 int rram_f32_engine_for_ip(int M, int N, int K, size_t ws_bytes);
+/* Engine of the convolution weight gradient (conv_layer.cu:35-44, the weight
+ * GEMM), process-wide.  RRAM_ENGINE_F32 (default): the fp32-MFMA GEMM with
+ * the column matrix gathered in the kernel, exactly as without this selector.
+ * RRAM_ENGINE_BF16X6: stride 1, dilation 1, square 3x3 / 5x5 kernels with
+ * pad <= k - 1 (any group count, channel counts and plane size) run
+ * wgrad_x6<K,GR> on v_mfma_f32_32x32x16_bf16 (both operands split in the
+ * kernel, split-K partials in the workspace summed in a fixed order: the same
+ * call gives the same bits); db then comes from the bias kernels.  Every
+ * other shape, and a workspace below the plan's partials, keeps the fp32
+ * path.  Returns the previous engine, or RRAM_EINVAL for an unknown one.
+ * rram_bwd_weight_engine_for_conv: the engine rram_conv2d_bwd(_ex) would use
+ * for d's weight gradient right now with ws_bytes of workspace (host only).
+ * rram_conv_wgrad_kernel_list: every instantiated wgrad_x6 kernel, one id per
+ * line (snprintf style); rram_conv_bwd_kernel_ids reports the one that runs
+ * as wgrad_x6<K,GR>/sS (S splits). */
+int rram_set_bwd_weight_engine(int engine);
+int rram_get_bwd_weight_engine(void);
+int rram_bwd_weight_engine_for_conv(const rram_conv_desc* d, size_t ws_bytes);
+int rram_conv_wgrad_kernel_list(char* out, size_t cap);
 
 /* Bytes of device workspace the backward passes need for `images_per_chunk`
- * images (explicit im2col/col2im buffer). */
+ * images (explicit im2col/col2im buffer); with the weight gradient on
+ * RRAM_ENGINE_BF16X6 at least its partials too. */
 size_t rram_conv2d_bwd_workspace(const rram_conv_desc* d, int images_per_chunk);
 
 /* dw += conv weight gradient, db += bias gradient (db nullable);

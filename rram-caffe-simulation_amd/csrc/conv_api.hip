@@ -39,6 +39,11 @@ std::atomic<uint64_t>& scratch_gen();
 int pack_octets(const float* x, void* oct, int num, int C, int HWi, hipStream_t s);
 std::atomic<int>& f32_engine();
 std::string f32_kernel_list();
+std::atomic<int>& bwd_weight_engine();
+size_t conv_bwd_weight_x6_bytes(const rram_conv_desc* d);
+int conv_bwd_weight_x6(const rram_conv_desc* d, const float* x, const float* dy, float* dw, void* part,
+                       size_t part_bytes, hipStream_t s);
+std::string conv_wgrad_kernel_list();
 
 namespace {
 
@@ -169,6 +174,22 @@ int rram_set_f32_engine(int engine) {
 }
 
 int rram_get_f32_engine(void) { return rram::f32_engine().load(); }
+
+int rram_set_bwd_weight_engine(int engine) {
+  RRAM_REQUIRE(engine == RRAM_ENGINE_F32 || engine == RRAM_ENGINE_BF16X6, "bwd weight engine: unknown engine");
+  return rram::bwd_weight_engine().exchange(engine);
+}
+
+int rram_get_bwd_weight_engine(void) { return rram::bwd_weight_engine().load(); }
+
+int rram_bwd_weight_engine_for_conv(const rram_conv_desc* d_in, size_t ws_bytes) {
+  if (d_in == nullptr || rram::bwd_weight_engine().load() != RRAM_ENGINE_BF16X6) return RRAM_ENGINE_F32;
+  rram_conv_desc d = *d_in;
+  if (rram_conv_out_shape(&d) != RRAM_OK) return RRAM_ENGINE_F32;
+  // the plan's split is never cut to fit: a workspace below it keeps the fp32 path
+  const size_t need = rram::conv_bwd_weight_x6_bytes(&d);
+  return need > 0 && ws_bytes >= need ? RRAM_ENGINE_BF16X6 : RRAM_ENGINE_F32;
+}
 
 int rram_gemm_f32_ex(int trans_a, int trans_b, int M, int N, int K, float alpha, const float* A,
                      int lda, const float* B, int ldb, float beta, float* C, int ldc,
@@ -334,7 +355,9 @@ static BwdColPlan bwd_col_plan(const rram_conv_desc& d, size_t ws_bytes, bool wa
 size_t rram_conv2d_bwd_workspace(const rram_conv_desc* d_in, int images_per_chunk) {
   rram_conv_desc d = *d_in;
   if (rram_conv_out_shape(&d) != RRAM_OK || images_per_chunk < 1) return 0;
-  return col_bytes(d, images_per_chunk) + bwd_part_bytes(d, images_per_chunk);
+  const size_t f32 = col_bytes(d, images_per_chunk) + bwd_part_bytes(d, images_per_chunk);
+  if (rram::bwd_weight_engine().load() != RRAM_ENGINE_BF16X6) return f32;
+  return std::max(f32, rram::conv_bwd_weight_x6_bytes(&d));
 }
 
 int rram_conv2d_bwd(const rram_conv_desc* d_in, const float* x, const float* w, const float* dy,
@@ -366,9 +389,12 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
   // The weight gradient gathers its column matrix inside the GEMM
   // (conv_bwd_weight_im2t: no im2col pass, all images in one split GEMM) when
   // the workspace holds its split-K partials; else the column path below.
-  const bool im2t = dw && x && w && ws && conv_bwd_weight_im2t_ok(&d, ws_bytes);
+  // (rram_set_bwd_weight_engine(RRAM_ENGINE_BF16X6): the stride-1 3x3 / 5x5
+  // weight gradient on the bf16x6 engine instead, the bias gradient unfolded)
+  const bool wx6 = dw && x && w && ws && rram_bwd_weight_engine_for_conv(&d, ws_bytes) == RRAM_ENGINE_BF16X6;
+  const bool im2t = !wx6 && dw && x && w && ws && conv_bwd_weight_im2t_ok(&d, ws_bytes);
   bool fold_db = im2t && db && d.group == 1;
-  if (!im2t && db && dw && x && w && ws && d.group == 1 && HoWo >= 2 * 32)
+  if (!im2t && !wx6 && db && dw && x && w && ws && d.group == 1 && HoWo >= 2 * 32)
     fold_db = bwd_col_plan(d, ws_bytes, true).part_bytes > 0;
   if (db && !fold_db) {
     const int S = d.num < 64 ? d.num : 64;
@@ -427,6 +453,11 @@ int rram_conv2d_bwd_ex(const rram_conv_desc* d_in, const float* x, const float* 
                  t.out_h, t.out_w, d.height, d.width);
     return conv_fwd_core(&t, dy, wt, nullptr, dx, 0, s);
   };
+  if (wx6) {
+    rc = conv_bwd_weight_x6(&d, x, dy, dw, ws, ws_bytes, s);
+    if (rc) return rc;
+    dw = nullptr;  // done
+  }
   if (im2t) {
     rc = conv_bwd_weight_im2t(&d, x, dy, dw, fold_db ? db : nullptr, ws, ws_bytes, s);
     if (rc) return rc;
@@ -658,5 +689,7 @@ int rram_conv_bwd_kernel_ids(const rram_conv_desc* d, int want_dw, int want_db, 
 }
 
 int rram_f32_kernel_list(char* out, size_t cap) { return copy_text(rram::f32_kernel_list(), out, cap); }
+
+int rram_conv_wgrad_kernel_list(char* out, size_t cap) { return copy_text(rram::conv_wgrad_kernel_list(), out, cap); }
 
 }  // extern "C"

@@ -73,6 +73,24 @@ __device__ __forceinline__ void store_terms8(const float (&v)[8], char* dst) {
   *reinterpret_cast<bf16x8*>(dst + 16) = t.m;
   *reinterpret_cast<bf16x8*>(dst + 32) = t.l;
 }
+// The six products of a * b in the engine's accumulation order (smallest
+// terms first): al*bh + ah*bl + am*bm + am*bh + ah*bm + ah*bh on
+// v_mfma_f32_32x32x16_bf16 (a product of two bf16 is exact in fp32).
+// RRAM_X6_DROP = k (1..5) leaves out the k-th product below.  Guard
+// validation only (profiles/r04_fp32_guard.txt: a build with a term dropped
+// must fail tests/test_gpu_fp32_guard.py); the product build has it 0.
+#ifndef RRAM_X6_DROP
+#define RRAM_X6_DROP 0
+#endif
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x16 mfma6(const Parts& a, const Parts& b, f32x16 c) {
+  if (RRAM_X6_DROP != 1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, c, 0, 0, 0);
+  if (RRAM_X6_DROP != 2) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, c, 0, 0, 0);
+  if (RRAM_X6_DROP != 3) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, c, 0, 0, 0);
+  if (RRAM_X6_DROP != 4) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, c, 0, 0, 0);
+  if (RRAM_X6_DROP != 5) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
+}
 }  // namespace x6
 }  // namespace
 }  // namespace rram

@@ -96,6 +96,10 @@ SIGNATURES = {
     "rram_get_f32_engine": (I, []),
     "rram_f32_engine_for_conv": (I, [P]),
     "rram_f32_engine_for_ip": (I, [I, I, I, SZ]),
+    "rram_set_bwd_weight_engine": (I, [I]),
+    "rram_get_bwd_weight_engine": (I, []),
+    "rram_bwd_weight_engine_for_conv": (I, [P, SZ]),
+    "rram_conv_wgrad_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_conv_output_octets_only": (I, [P]),
     "rram_fault_threshold": (I, [P, I64, F, F, P]),
     "rram_fault_init": (I, [P, P, I64, F, F, U64, U64, U64, U32, U32, P]),

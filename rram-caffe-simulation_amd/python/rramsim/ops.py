@@ -251,6 +251,33 @@ def f32_engine_for_ip(M, N, K, ws_bytes=256 << 20):
     return _lib().rram_f32_engine_for_ip(int(M), int(N), int(K), int(ws_bytes))
 
 
+def set_bwd_weight_engine(engine):
+    """Engine of the convolution weight gradient (rram_set_bwd_weight_engine):
+    ENGINE_F32 (default) or ENGINE_BF16X6 for the stride-1 3x3 / 5x5 shapes;
+    returns the previous one."""
+    prev = _lib().rram_set_bwd_weight_engine(int(engine))
+    if prev < 0:
+        K.check(prev, "set_bwd_weight_engine")
+    return prev
+
+
+def get_bwd_weight_engine():
+    return _lib().rram_get_bwd_weight_engine()
+
+
+def bwd_weight_engine_for_conv(d, ws_bytes):
+    """Engine conv2d_bwd would use for d's weight gradient now with ws_bytes of workspace."""
+    return _lib().rram_bwd_weight_engine_for_conv(C.byref(d), int(ws_bytes))
+
+
+def conv_wgrad_kernel_list():
+    """Ids of every instantiated bf16x6 weight-gradient kernel (no /sS split suffix)."""
+    n = _lib().rram_conv_wgrad_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_conv_wgrad_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
 def conv2d_fwd(d, x, w, bias, y, relu=False):
     K.check(_lib().rram_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(y), int(relu),
                                    _stream()), "conv2d_fwd")
