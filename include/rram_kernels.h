@@ -664,6 +664,41 @@ int rram_ip_fwd_groups(const float* x, const float* w, int64_t w_group_stride, c
                        void* ws, size_t ws_bytes, rram_stream_t stream);
 int rram_ip_fwd_groups_fused(int G, int M, int N, int K, int transpose, size_t ws_bytes);
 
+/* The crossbar-tiled InnerProduct forward (no reference counterpart; DESIGN
+ * §7.4): W [N][K] sits on arrays of `rows` rows, so the K axis is cut into
+ * ceil(K / rows) crossbar tiles (the last may be short).  Each tile's partial
+ * sum p_t = sum x'[m][k] W[n][k] is formed in fp32 on the bf16x6 engine's
+ * product order from zero, digitised by an ADC of adc_bits bits,
+ *   qmax = 2^(adc_bits-1) - 1, step = adc_range / qmax,
+ *   q_t = clamp(rint(p_t / step), -qmax, qmax)   (half to even; the kernel
+ *         multiplies by the reciprocal, both computed in double on the host),
+ * and only the codes are summed, as int32: y = float(sum_t q_t) * step + bias,
+ * then ReLU.  dac_bits > 0 quantises the activations first:
+ *   xs = dac_range / (2^(dac_bits-1) - 1), x' = clamp(rint(x / xs), +-(2^(dac_bits-1) - 1)) * xs.
+ * rows: a multiple of 32 in [32, 1024]; adc_bits in [2, 16]; dac_bits 0 or in
+ * [2, 16]; the ranges finite and > 0; transpose must be 0: anything else is
+ * RRAM_EINVAL before the device is touched.  Any M, N >= 0, K >= 1, M * N <
+ * 2^31, any 4-byte operand alignment.
+ * split_k: 0 = the planner's split over K (whole tiles, its int32 partials
+ * within ws_bytes), else that many splits, clamped to the tile count, for
+ * which a workspace below rram_ip_fwd_xbar_workspace(..., split_k) bytes is
+ * RRAM_EINVAL.  The sum is an integer: every split gives the same bits.
+ * rram_ip_fwd_xbar_workspace: the bytes split_k needs (0 = the most the
+ * planner would use).  rram_ip_fwd_xbar_kernel_ids (host only): one line per
+ * launch, snprintf style as above: xbar:pack<vec|scalar>, xbar:ip<vec|scalar>/sS,
+ * and xbar:finish when S > 1 (vec: that operand is 16-byte aligned and K % 4 == 0). */
+typedef struct {
+  int32_t rows, adc_bits;
+  float adc_range;
+  int32_t dac_bits;
+  float dac_range;
+} rram_xbar_cfg;
+int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int transpose,
+                     const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes, rram_stream_t stream);
+size_t rram_ip_fwd_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
+int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
+                                int split_k, size_t ws_bytes, char* out, size_t cap);
+
 /* dw += ..., db += ... (nullable), dx = ... (nullable). */
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw,
                 float* db, float* dx, int M, int N, int K, int transpose,

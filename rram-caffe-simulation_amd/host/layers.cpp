@@ -376,6 +376,41 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
     FillBlob(this->blobs_[1].get(), ip.sub_or_empty("bias_filler"), seed, 1);
   }
   this->param_propagate_down_.assign(this->blobs_.size(), true);
+  // crossbar_param { rows adc_bits adc_range [dac_bits dac_range] }, or the Net
+  // option `crossbar` ("rows,adc_bits,adc_range[,dac_bits,dac_range]", handed
+  // down as rram_crossbar to layers without the message)
+  const Msg* xp = this->layer_param_.sub("crossbar_param");
+  xbar_on_ = xp != nullptr || this->layer_param_.has("rram_crossbar");
+  if (xbar_on_) {
+    xbar_ = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
+    if (xp != nullptr) {
+      xbar_.rows = static_cast<int32_t>(xp->integer("rows", 0));
+      xbar_.adc_bits = static_cast<int32_t>(xp->integer("adc_bits", 0));
+      xbar_.adc_range = static_cast<float>(xp->num("adc_range", 0.0));
+      xbar_.dac_bits = static_cast<int32_t>(xp->integer("dac_bits", 0));
+      xbar_.dac_range = static_cast<float>(xp->num("dac_range", 1.0));
+    } else {
+      std::vector<double> v;
+      std::stringstream ss(this->layer_param_.str("rram_crossbar"));
+      std::string t;
+      try {
+        while (std::getline(ss, t, ',')) v.push_back(std::stod(t));
+      } catch (const std::exception&) {
+        v.clear();
+      }
+      CAFFE_CHECK(v.size() == 3 || v.size() == 5, this->name() << ": option crossbar wants "
+                                                               << "rows,adc_bits,adc_range[,dac_bits,dac_range]");
+      xbar_.rows = static_cast<int32_t>(v[0]);
+      xbar_.adc_bits = static_cast<int32_t>(v[1]);
+      xbar_.adc_range = static_cast<float>(v[2]);
+      if (v.size() == 5) xbar_.dac_bits = static_cast<int32_t>(v[3]), xbar_.dac_range = static_cast<float>(v[4]);
+    }
+    // the kernel library's own checks of the configuration, on a host-only plan query
+    CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
+    char id[8];
+    CAFFE_CHECK(rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id) > 0,
+                this->name() << ": crossbar_param: " << rram_last_error());
+  }
 }
 
 template <typename Dtype>
@@ -391,7 +426,7 @@ void InnerProductLayer<Dtype>::Reshape(const std::vector<Blob<Dtype>*>& bottom,
   // reduce: fc6 -> fc7), key = (M, K, rows per tile)
   in_rows_key_ = 0;
   int bmc = 0;
-  const size_t rb = (this->phase_ == TEST && !transpose_ && groups_ == 1)
+  const size_t rb = (this->phase_ == TEST && !transpose_ && groups_ == 1 && !xbar_on_)
                         ? rram_ip_rows_pack_bytes(M_, N_, K_, ws_request(), &bmc)
                         : 0;
   if (rb > 0 && bmc > 0 && bmc < 4096) {
@@ -405,6 +440,19 @@ template <typename Dtype>
 void InnerProductLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bottom,
                                            const std::vector<Blob<Dtype>*>& top) {
   void* ws = Caffe::workspace(ws_request());
+  if (xbar_on_) {  // the crossbar read-out, per map group with that group's weights and bias
+    CAFFE_CHECK(M_ % groups_ == 0, this->name() << ": " << M_ << " rows do not split into " << groups_ << " map groups");
+    const int Mg = M_ / groups_;
+    const Dtype* w = group_param_[0] ? group_param_[0] : this->blobs_[0]->gpu_data();
+    const Dtype* b = !bias_term_ ? nullptr : group_param_[1] ? group_param_[1] : this->blobs_[1]->gpu_data();
+    const Dtype* x = bottom[0]->gpu_data();
+    Dtype* y = top[0]->mutable_gpu_data();
+    for (int g = 0; g < groups_; ++g)
+      RRAM_CALL(rram_ip_fwd_xbar(x + (int64_t)g * Mg * K_, w + g * group_stride_[0], b ? b + g * group_stride_[1] : b,
+                                 y + (int64_t)g * Mg * N_, Mg, N_, K_, 0, &xbar_, fused_relu ? 1 : 0, 0, ws,
+                                 Caffe::workspace_size(), Caffe::stream()));
+    return;
+  }
   if (groups_ > 1) {  // map groups: no packed-row shortcut (rram_ip_fwd_groups has no rows form)
     CAFFE_CHECK(M_ % groups_ == 0, this->name() << ": " << M_ << " rows do not split into " << groups_ << " map groups");
     const Dtype* w = group_param_[0] ? group_param_[0] : this->blobs_[0]->gpu_data();

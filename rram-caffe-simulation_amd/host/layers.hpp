@@ -107,8 +107,17 @@ class InnerProductLayer : public Layer<Dtype> {
                     const std::vector<Blob<Dtype>*>& bottom) override;
   int M_ = 0, N_ = 0, K_ = 0, axis_ = 1;
   bool bias_term_ = true, transpose_ = false;
-  // split-K partials need up to 16 x M x N floats (<= 256 MB)
-  size_t ws_request() const { return std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20); }
+  // split-K partials need up to 16 x M x N floats (<= 256 MB); the crossbar
+  // forward its planner's int32 partials
+  size_t ws_request() const {
+    const size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
+    if (!xbar_on_) return f32;
+    return std::max(f32, rram_ip_fwd_xbar_workspace(M_ / groups_, N_, K_, &xbar_, 0));
+  }
+  // crossbar_param (or the Net option `crossbar`): the forward is the
+  // crossbar-tiled ADC read-out (rram_ip_fwd_xbar), the backward unchanged
+  bool xbar_on_ = false;
+  rram_xbar_cfg xbar_{};
   uint64_t in_rows_key_ = 0;  // the packed-row companion this layer reads (Reshape; 0: none)
   // set_map_groups: the batch rows are groups_ groups of M_ / groups_ rows,
   // group g reading copy g of a faulted blob (nullptr: the layer's own blob)

@@ -188,6 +188,9 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
       lp.set("rram_solver_rank", options.str("solver_rank", "0"));
       lp.set("rram_solver_count", options.str("solver_count", "1"));
     }
+    // option crossbar: every InnerProduct layer without a crossbar_param of its own
+    if (type == "InnerProduct" && options.has("crossbar") && lp.sub("crossbar_param") == nullptr)
+      lp.set("rram_crossbar", options.str("crossbar"));
     auto layer = LayerRegistry<Dtype>::CreateLayer(lp);
     layer->layer_id = static_cast<uint32_t>(lid);
     const std::string lname = lp.str("name");

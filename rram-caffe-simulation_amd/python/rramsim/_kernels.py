@@ -84,6 +84,12 @@ class ConvDesc(C.Structure):
         "pad_w", "stride_h", "stride_w", "dilation_h", "dilation_w", "group", "out_h", "out_w")]
 
 
+class XbarCfg(C.Structure):
+    """rram_xbar_cfg: crossbar rows, ADC bits / range, DAC bits (0: none) / range."""
+    _fields_ = [("rows", C.c_int32), ("adc_bits", C.c_int32), ("adc_range", C.c_float),
+                ("dac_bits", C.c_int32), ("dac_range", C.c_float)]
+
+
 # (name, restype, argtypes) for every symbol of include/rram_kernels.h
 P, I, I64, U32, U64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -166,6 +172,9 @@ SIGNATURES = {
     "rram_col2im": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P, P]),
     "rram_ip_fwd": (I, [P, P, P, P, I, I, I, I, I, P, SZ, P]),
     "rram_ip_bwd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
+    "rram_ip_fwd_xbar": (I, [P, P, P, P, I, I, I, I, P, I, I, P, SZ, P]),
+    "rram_ip_fwd_xbar_workspace": (SZ, [I, I, I, P, I]),
+    "rram_ip_fwd_xbar_kernel_ids": (I, [I, I, I, P, I, I, I, SZ, C.c_char_p, SZ]),
     "rram_ip_rows_pack_bytes": (SZ, [I, I, I, SZ, P]),
     "rram_ip_fwd_rows": (I, [P, P, P, P, P, P, I, I, I, I, I, P, SZ, P, P]),
     "rram_relu_fwd": (I, [P, P, I64, F, P]),

@@ -439,6 +439,27 @@ def ip_fwd(x, w, bias, y, M, N, K_, transpose=False, relu=False, workspace=None)
                                _p(workspace), wsb, _stream()), "ip_fwd")
 
 
+def xbar_cfg(rows, adc_bits, adc_range, dac_bits=0, dac_range=1.0):
+    """rram_xbar_cfg of the crossbar-tiled InnerProduct forward (ip_fwd_xbar)."""
+    return K.XbarCfg(rows, adc_bits, adc_range, dac_bits, dac_range)
+
+
+def ip_fwd_xbar(x, w, bias, y, M, N, K_, cfg, transpose=False, relu=False, split_k=0, workspace=None):
+    """rram_ip_fwd_xbar: y = the ADC read-out of x . w^T from crossbars of cfg.rows rows (split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_fwd_xbar(_p(x), _p(w), _p(bias), _p(y), M, N, K_, int(transpose), C.byref(cfg), int(relu),
+                                    split_k, _p(workspace), wsb, _stream()), "ip_fwd_xbar")
+
+
+def ip_fwd_xbar_workspace(M, N, K_, cfg, split_k=0):
+    return _lib().rram_ip_fwd_xbar_workspace(M, N, K_, C.byref(cfg), split_k)
+
+
+def ip_fwd_xbar_kernel_ids(M, N, K_, cfg, x_align16=True, w_align16=True, split_k=0, ws_bytes=0):
+    return _id_lines(_lib().rram_ip_fwd_xbar_kernel_ids, M, N, K_, C.byref(cfg), int(x_align16), int(w_align16),
+                     split_k, int(ws_bytes))
+
+
 def ip_rows_pack_bytes(M, N, K_, ws_bytes):
     """(bytes, rows per tile) of the bf16x6 engine's packed-row input form (0, 0: not served)."""
     bmc = C.c_int(0)
