@@ -698,6 +698,32 @@ int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y
 size_t rram_ip_fwd_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
 int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                 int split_k, size_t ws_bytes, char* out, size_t cap);
+/* The crossbar-tiled Convolution forward (no reference counterpart; DESIGN
+ * §7.5): the array of group g holds the unrolled kernel, rows
+ * k = (ci * kernel_h + i) * kernel_w + j (Caffe's im2col / weight-blob order),
+ * Kg = channels / group * kernel_h * kernel_w of them, against that group's
+ * output channels.  Crossbar tile t is rows [t * rows, (t + 1) * rows) of one
+ * group (the last may be short; a boundary usually falls inside a channel's
+ * taps).  Per output (n, co, oh, ow) and tile the partial sum over the
+ * zero-padded taps is formed and digitised exactly as in rram_ip_fwd_xbar
+ * (DAC on each input value, padding stays 0; ADC; int32 sum of the codes;
+ * y = float(S) * step + bias[co]; ReLU); y is dense NCHW.  There is no im2col
+ * buffer: the gather is part of the kernel's LDS fill.
+ * d: any descriptor rram_conv_out_shape accepts, num * num_output * out_h *
+ * out_w < 2^31; cfg and split_k under rram_ip_fwd_xbar's rules; num == 0 is
+ * RRAM_OK with no launch; every refusal is RRAM_EINVAL before the device is
+ * touched.  Every split and every batch size give the same bits per image.
+ * rram_conv2d_fwd_xbar_workspace: the bytes split_k needs (0 = the most the
+ * planner would use).  rram_conv2d_fwd_xbar_kernel_ids (host only):
+ * xbar:conv<vec|scalar>/sS, and xbar:finish when S > 1 (vec: w is 16-byte
+ * aligned and Kg % 4 == 0; x is gathered with 4-byte loads at any alignment,
+ * so x_align16 does not change the ids). */
+int rram_conv2d_fwd_xbar(const rram_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                         const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
+                         rram_stream_t stream);
+size_t rram_conv2d_fwd_xbar_workspace(const rram_conv_desc* d, const rram_xbar_cfg* cfg, int split_k);
+int rram_conv2d_fwd_xbar_kernel_ids(const rram_conv_desc* d, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
+                                    int split_k, size_t ws_bytes, char* out, size_t cap);
 
 /* dw += ..., db += ... (nullable), dx = ... (nullable). */
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw,

@@ -26,6 +26,9 @@
 // split in registers after the LDS read, each wave only its own 32 columns.
 // Two LDS stages: the global loads of K-step s + 1 are issued before the MFMAs
 // of step s and land in LDS after them, one barrier per step.
+//
+// The crossbar-tiled Convolution forward (k_conv_xbar) is the same
+// array with the unrolled kernel as its rows: see the comment above the kernel.
 #include <algorithm>
 #include <cmath>
 
@@ -73,6 +76,14 @@ __device__ __forceinline__ float xbar_out(int32_t S, float step, const float* bi
   return relu ? fmaxf(o, 0.0f) : o;
 }
 
+// the DAC on a run of 8 inputs: clamp(rint(v / xs), +-qmax) * xs (qmax = 0: none); 0 stays 0
+__device__ __forceinline__ void dac8(float (&v)[8], float xs, float qmax) {
+  if (qmax > 0.0f) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = __fmul_rn(__builtin_amdgcn_fmed3f(__builtin_rintf(v[j] / xs), -qmax, qmax), xs);
+  }
+}
+
 // x [M][K] fp32 -> DAC -> bf16 terms in the K-step slabs k_ip_xbar copies to
 // LDS (zero past M and K).  One thread per (row, K-step, group, half): 8
 // activations in, 48 bytes out.  dac_qmax = 0: no DAC.
@@ -101,11 +112,7 @@ __global__ void __launch_bounds__(256) k_xbar_pack(const float* __restrict__ x, 
           if (k + j < K) v[j] = src[j];
       }
     }
-    if (dac_qmax > 0.0f) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        v[j] = __fmul_rn(__builtin_amdgcn_fmed3f(__builtin_rintf(v[j] / dac_xs), -dac_qmax, dac_qmax), dac_xs);
-    }
+    dac8(v, dac_xs, dac_qmax);
     const int64_t tm = mrow / BM;
     const int row = static_cast<int>(mrow - tm * BM);
     char* rowp = out + ((tm * ksteps + ks) * BM + row) * RLB;
@@ -254,34 +261,301 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 }
 
-// y = the read-out of the summed int32 slabs [split][M][N]
+// The crossbar-tiled Convolution forward.  The array of group g
+// has the unrolled kernel as its rows, k = (ci * kh + i) * kw + j (the row order
+// of Caffe's im2col and of the weight blob), Kg = C/group * kh * kw of them,
+// against the group's output channels; crossbar tile t holds rows [t R, (t + 1) R),
+// the last may be short, and a tile boundary falls wherever t R falls in that
+// order.  There is no im2col buffer: the gather is the LDS fill.
+//
+// Roles.  An output position is a flattened (n, oh, ow), so a tile of 128
+// positions runs across rows and images.  The positions are the MFMA column
+// operand and the output channels the row operand (k_ip_xbar's roles swapped):
+// a lane of the 32 x 32 accumulator then holds one position and 16 channels,
+// and a store instruction writes 32 consecutive positions (consecutive ow) of
+// a channel plane.  With k_ip_xbar's roles the lanes would run along the
+// channels, a stride of Ho * Wo floats between lanes.
+//
+// Work split.  A workgroup (4 waves) owns 128 positions x 128 output channels
+// of one group for a range of whole crossbar tiles.  Wave v owns channels
+// 32 v .. 32 v + 31 for all 128 positions: four 32 x 32 blocks, each with the
+// fp32 set of the current tile and the int32 set S, the ADC in registers at
+// the tile boundary as in k_ip_xbar.
+//
+// Staging, per K-step of 32 k.  Thread (p = tid & 127, h = tid >> 7) gathers
+// the 16 values k = 32 s + 16 h .. + 15 of position p straight from x: k is
+// decomposed into (ci, i, j) once (FastDiv) and advanced incrementally, a
+// padding tap, a position past M and k past Kg are zeros by predicate (the
+// load then reads the group's first element, never an out-of-range address).
+// Consecutive lanes take consecutive positions, so a stride-1 row is one
+// coalesced request.  When the loads have landed (after the MFMAs of the
+// current step) the thread applies the DAC, splits each run of 8 once and
+// writes the two 48-byte term groups (MFMA group g = 0, 1, lane half h) of
+// k_ip_xbar's 208-byte row.  The weights of the group are the [Cout/group][Kg]
+// matrix k_ip_xbar streams: fp32 from HBM, split after the LDS read.
+struct ConvPlan {
+  const float* x;
+  const float* w;
+  const float* bias;
+  float* y;
+  int32_t* part;       // int32 slabs [split][num][Cout][Ho][Wo] (split > 1)
+  int H, W, KH, KW, ph, pw, sh, sw, dh, dw, Wo;
+  int HW, HoWo;
+  int Cin, Cout;       // all groups
+  int Cg, Ng;          // input / output channels of one group
+  int M, Kg;           // positions num * Ho * Wo, rows of one group's array
+  FastDiv khkw, kw_div, howo, wo_div;
+  int tiles_p, tiles_c, groups;
+  int ksteps, spt, ntiles, tc, split;
+  int64_t total;       // num * Cout * Ho * Wo
+  float step, inv_step, qmax, dac_xs, dac_qmax;
+  int relu;
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_conv_xbar(ConvPlan P) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  int id = xcd_tile_id(blockIdx.x, gridDim.x);
+  const int tp = __builtin_amdgcn_readfirstlane(id % P.tiles_p);
+  id /= P.tiles_p;
+  const int tn = __builtin_amdgcn_readfirstlane(id % P.tiles_c);
+  id /= P.tiles_c;
+  const int grp = __builtin_amdgcn_readfirstlane(id % P.groups);
+  const int z = __builtin_amdgcn_readfirstlane(id / P.groups);
+  const int p0 = tp * BM, c0 = tn * BN;
+  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
+  const int s0 = t0 * P.spt, s1 = min(P.ksteps, t1 * P.spt);
+
+  // the gather: this thread's position and its corner (oh sh - ph, ow sw - pw)
+  const int gp = tid & (BM - 1), gh = tid >> 7;
+  const bool pvalid = p0 + gp < P.M;
+  const uint32_t gpos = pvalid ? static_cast<uint32_t>(p0 + gp) : 0u;
+  const uint32_t gn = fdiv(gpos, P.howo), gsp = gpos - gn * P.HoWo;
+  const uint32_t goh = fdiv(gsp, P.wo_div), gow = gsp - goh * P.Wo;
+  const int hb = static_cast<int>(goh) * P.sh - P.ph, wb = static_cast<int>(gow) * P.sw - P.pw;
+  const float* xg = P.x + ((int64_t)gn * P.Cin + (int64_t)grp * P.Cg) * P.HW;  // image gn, first channel of the group
+  const int corner = hb * P.W + wb;
+  const int row_step = P.dh * P.W - P.KW * P.dw;        // offset step from tap (i, kw) to (i + 1, 0)
+  const int chan_step = P.HW - P.KH * P.dh * P.W;       // ... from tap (kh, 0) of ci to (0, 0) of ci + 1
+
+  // the weights: B_LD quads (row, 4 k) of the group's [Ng][Kg] matrix
+  const float* bsrc[B_LD];
+  int bq[B_LD], blds[B_LD];
+#pragma unroll
+  for (int i = 0; i < B_LD; ++i) {
+    const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
+    bsrc[i] = c0 + row < P.Ng ? P.w + ((int64_t)grp * P.Ng + c0 + row) * P.Kg + 4 * q : nullptr;
+    bq[i] = 4 * q;
+    blds[i] = A_B + row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4);
+  }
+  float rx[16];
+  float4 rb[B_LD];
+  auto gload = [&](int s) {
+    const int k0 = s * KS + 16 * gh;
+    const uint32_t ci = fdiv(static_cast<uint32_t>(k0), P.khkw), rem = static_cast<uint32_t>(k0) - ci * P.khkw.d;
+    int ki = static_cast<int>(fdiv(rem, P.kw_div));
+    int kj = static_cast<int>(rem) - ki * P.KW;
+    int ih = hb + ki * P.dh, iw = wb + kj * P.dw;
+    int off = static_cast<int>(ci) * P.HW + ki * P.dh * P.W + kj * P.dw;  // of tap (ci, ki, kj) from the corner
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const bool ok = pvalid && k0 + u < P.Kg && static_cast<uint32_t>(ih) < static_cast<uint32_t>(P.H) &&
+                      static_cast<uint32_t>(iw) < static_cast<uint32_t>(P.W);
+      const float v = xg[ok ? corner + off : 0];
+      rx[u] = ok ? v : 0.0f;
+      ++kj, iw += P.dw, off += P.dw;
+      if (kj == P.KW) {
+        kj = 0, iw = wb, ++ki, ih += P.dh, off += row_step;
+        if (ki == P.KH) ki = 0, ih = hb, off += chan_step;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+      const int k = s * KS + bq[i];
+      float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (bsrc[i] != nullptr) {
+        const float* p = bsrc[i] + s * KS;
+        if (VEC) {  // Kg % 4 == 0, w 16-byte aligned
+          if (k < P.Kg) f = *reinterpret_cast<const float4*>(p);
+        } else {
+          if (k < P.Kg) f.x = p[0];
+          if (k + 1 < P.Kg) f.y = p[1];
+          if (k + 2 < P.Kg) f.z = p[2];
+          if (k + 3 < P.Kg) f.w = p[3];
+        }
+      }
+      rb[i] = f;
+    }
+  };
+  auto lstore = [&](char* st) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = rx[8 * g + j];
+      dac8(v, P.dac_xs, P.dac_qmax);
+      x6::store_terms8(v, st + gp * RLB + (g * 2 + gh) * 48);
+    }
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4*>(st + blds[i]) = rb[i];
+  };
+
+  floatx16 acc[MI];   // the current crossbar tile's partial sums
+  int32_t S[MI][16];  // the digital sum of the ADC codes
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[i][r] = 0.0f;
+      S[i][r] = 0;
+    }
+
+  const int nw = 32 * wave + lr;  // this lane's weight row (output channel) inside the tile
+  auto compute = [&](const char* st) {
+    const float* sb = reinterpret_cast<const float*>(st + A_B) + nw * KS;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      float b[8];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
+        b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
+      }
+      x6::Parts wp;
+      x6::split8_safe(b, wp);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const char* p = st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48;
+        const x6::Parts xp{*reinterpret_cast<const x6::bf16x8*>(p), *reinterpret_cast<const x6::bf16x8*>(p + 16),
+                           *reinterpret_cast<const x6::bf16x8*>(p + 32)};
+        acc[i] = x6::mfma6(wp, xp, acc[i]);  // rows = channels, columns = positions
+      }
+    }
+  };
+  auto adc = [&]() {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(acc[i][r], P.inv_step)), -P.qmax, P.qmax);
+        S[i][r] += static_cast<int32_t>(q);
+        acc[i][r] = 0.0f;
+      }
+  };
+
+  gload(s0);
+  lstore(smem);
+  __syncthreads();
+  int in_tile = 0;
+  for (int s = s0; s < s1; ++s) {
+    const int cur = (s - s0) & 1;
+    const bool more = s + 1 < s1;
+    if (more) gload(s + 1);
+    compute(smem + cur * STAGE);
+    if (++in_tile == P.spt) {
+      adc();
+      in_tile = 0;
+    }
+    if (more) lstore(smem + (cur ^ 1) * STAGE);
+    __syncthreads();
+  }
+  if (in_tile != 0) adc();  // the short last tile
+
+  // lane (lr, lh) holds position 32 i + lr, channels 32 wave + 8 (r >> 2) + 4 lh + (r & 3)
+  int32_t* part = P.split > 1 ? P.part + (int64_t)z * P.total : nullptr;
+  const float* bias = P.bias != nullptr ? P.bias + grp * P.Ng : nullptr;
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int pos = p0 + 32 * i + lr;
+    if (pos >= P.M) continue;
+    const uint32_t n = fdiv(static_cast<uint32_t>(pos), P.howo), sp = static_cast<uint32_t>(pos) - n * P.HoWo;
+    const int64_t base = ((int64_t)n * P.Cout + (int64_t)grp * P.Ng) * P.HoWo + sp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = c0 + 32 * wave + 8 * (r >> 2) + 4 * lh + (r & 3);
+      if (co >= P.Ng) continue;
+      const int64_t o = base + (int64_t)co * P.HoWo;
+      if (part != nullptr)
+        part[o] = S[i][r];
+      else
+        P.y[o] = xbar_out(S[i][r], P.step, bias, co, P.relu);
+    }
+  }
+}
+
+// y = the read-out of the summed int32 slabs [split][M][N][inner] (inner = 1:
+// InnerProduct; Ho * Wo: a convolution's NCHW output with M = num, N = Cout)
 __global__ void __launch_bounds__(256) k_xbar_finish(const int32_t* __restrict__ part, int split, int M, int N,
-                                                     float step, const float* __restrict__ bias, int relu,
+                                                     int inner, float step, const float* __restrict__ bias, int relu,
                                                      float* __restrict__ y) {
-  const int64_t total = (int64_t)M * N;
+  const int64_t total = (int64_t)M * N * inner;
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     int32_t S = 0;
     for (int z = 0; z < split; ++z) S += part[z * total + idx];
-    y[idx] = xbar_out(S, step, bias, static_cast<int>(idx % N), relu);
+    y[idx] = xbar_out(S, step, bias, static_cast<int>((idx / inner) % N), relu);
   }
 }
 
 // The configuration's checks (host only) and the plan of a shape.
+int check_cfg(const rram_xbar_cfg* c, const char* who) {
+  RRAM_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+  RRAM_REQUIRE(c->rows >= 32 && c->rows <= 1024 && c->rows % 32 == 0,
+               "%s: rows %d not a multiple of 32 in [32, 1024]", who, c->rows);
+  RRAM_REQUIRE(c->adc_bits >= 2 && c->adc_bits <= 16, "%s: adc_bits %d outside [2, 16]", who, c->adc_bits);
+  RRAM_REQUIRE(std::isfinite(c->adc_range) && c->adc_range > 0.0f, "%s: adc_range must be finite and > 0", who);
+  RRAM_REQUIRE(c->dac_bits == 0 || (c->dac_bits >= 2 && c->dac_bits <= 16),
+               "%s: dac_bits %d neither 0 nor in [2, 16]", who, c->dac_bits);
+  RRAM_REQUIRE(c->dac_bits == 0 || (std::isfinite(c->dac_range) && c->dac_range > 0.0f),
+               "%s: dac_range must be finite and > 0", who);
+  return RRAM_OK;
+}
+
 int check(int M, int N, int K, const rram_xbar_cfg* c, int transpose) {
   RRAM_REQUIRE(c != nullptr, "ip_fwd_xbar: cfg is NULL");
   RRAM_REQUIRE(M >= 0 && N >= 0 && K >= 1, "ip_fwd_xbar: bad shape %d x %d x %d", M, N, K);
   RRAM_REQUIRE(!transpose, "ip_fwd_xbar: transposed weights are not served");
-  RRAM_REQUIRE(c->rows >= 32 && c->rows <= 1024 && c->rows % 32 == 0,
-               "ip_fwd_xbar: rows %d not a multiple of 32 in [32, 1024]", c->rows);
-  RRAM_REQUIRE(c->adc_bits >= 2 && c->adc_bits <= 16, "ip_fwd_xbar: adc_bits %d outside [2, 16]", c->adc_bits);
-  RRAM_REQUIRE(std::isfinite(c->adc_range) && c->adc_range > 0.0f, "ip_fwd_xbar: adc_range must be finite and > 0");
-  RRAM_REQUIRE(c->dac_bits == 0 || (c->dac_bits >= 2 && c->dac_bits <= 16),
-               "ip_fwd_xbar: dac_bits %d neither 0 nor in [2, 16]", c->dac_bits);
-  RRAM_REQUIRE(c->dac_bits == 0 || (std::isfinite(c->dac_range) && c->dac_range > 0.0f),
-               "ip_fwd_xbar: dac_range must be finite and > 0");
+  const int rc = check_cfg(c, "ip_fwd_xbar");
+  if (rc) return rc;
   RRAM_REQUIRE((int64_t)M * N < (1ll << 31), "ip_fwd_xbar: more than 2^31 outputs");
   return RRAM_OK;
+}
+
+// ADC step and DAC step of a configuration: computed in double, cast to float
+struct Steps {
+  float step, inv_step, qmax, dac_xs, dac_qmax;  // dac_qmax = 0: no DAC
+};
+Steps steps_of(const rram_xbar_cfg& c) {
+  Steps r{};
+  const int qmax = (1 << (c.adc_bits - 1)) - 1;
+  const double step = static_cast<double>(c.adc_range) / qmax;
+  r.step = static_cast<float>(step);
+  r.inv_step = static_cast<float>(1.0 / step);
+  r.qmax = static_cast<float>(qmax);
+  r.dac_xs = 1.0f;
+  if (c.dac_bits > 0) {
+    r.dac_qmax = static_cast<float>((1 << (c.dac_bits - 1)) - 1);
+    r.dac_xs = static_cast<float>(static_cast<double>(c.dac_range) / r.dac_qmax);
+  }
+  return r;
+}
+
+// splits of ntiles crossbar tiles: split_k = 0 toward 256 workgroups from
+// `tiles` output tiles with slabs of slab_bytes inside ws_bytes, else the
+// caller's split clamped to the tile count; whole tiles per split
+void plan_split(int ntiles, int64_t tiles, size_t slab_bytes, int split_k, size_t ws_bytes, int& tc, int& split) {
+  int s = split_k;
+  if (split_k <= 0) {
+    s = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, 256 / tiles)));
+    while (s > 1 && (size_t)s * slab_bytes > ws_bytes) --s;
+  }
+  s = std::max(1, std::min(s, ntiles));
+  tc = (ntiles + s - 1) / s;
+  split = (ntiles + tc - 1) / tc;
 }
 
 // split_k = 0: toward 256 workgroups, whole tiles, partials within ws_bytes;
@@ -294,23 +568,56 @@ void make_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t 
   P.ksteps = (K + KS - 1) / KS;
   P.spt = c.rows / KS;
   P.ntiles = (K + c.rows - 1) / c.rows;
-  int split = split_k;
-  if (split_k <= 0) {
-    const int64_t tiles = (int64_t)P.tiles_m * P.tiles_n;
-    split = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, 256 / tiles)));
-    while (split > 1 && (size_t)split * M * N * sizeof(int32_t) > ws_bytes) --split;
-  }
-  split = std::max(1, std::min(split, P.ntiles));
-  P.tc = (P.ntiles + split - 1) / split;
-  P.split = (P.ntiles + P.tc - 1) / P.tc;
-  const int qmax = (1 << (c.adc_bits - 1)) - 1;
-  const double step = static_cast<double>(c.adc_range) / qmax;
-  P.step = static_cast<float>(step);
-  P.inv_step = static_cast<float>(1.0 / step);
-  P.qmax = static_cast<float>(qmax);
+  plan_split(P.ntiles, (int64_t)P.tiles_m * P.tiles_n, (size_t)M * N * sizeof(int32_t), split_k, ws_bytes, P.tc,
+             P.split);
+  const Steps st = steps_of(c);
+  P.step = st.step, P.inv_step = st.inv_step, P.qmax = st.qmax;
 }
 
 size_t part_bytes(const Plan& P) { return P.split > 1 ? (size_t)P.split * P.M * P.N * sizeof(int32_t) : 0; }
+
+// The convolution's checks (host only; d gets its output shape) and plan.
+int conv_check(rram_conv_desc& d, const rram_xbar_cfg* c, int split_k) {
+  const int rc0 = check_cfg(c, "conv2d_fwd_xbar");
+  if (rc0) return rc0;
+  const int rc = rram_conv_out_shape(&d);
+  if (rc) return rc;
+  RRAM_REQUIRE(d.num >= 0, "conv2d_fwd_xbar: negative num");
+  RRAM_REQUIRE(split_k >= 0, "conv2d_fwd_xbar: negative split_k");
+  RRAM_REQUIRE((int64_t)d.num * d.num_output * d.out_h * d.out_w < (1ll << 31), "conv2d_fwd_xbar: more than 2^31 outputs");
+  RRAM_REQUIRE((int64_t)d.channels * d.height * d.width < (1ll << 30) &&
+                   (int64_t)d.channels / d.group * d.kernel_h * d.kernel_w < (1ll << 30),
+               "conv2d_fwd_xbar: an image or a kernel of 2^30 elements or more");
+  return RRAM_OK;
+}
+
+void make_conv_plan(const rram_conv_desc& d, const rram_xbar_cfg& c, int split_k, size_t ws_bytes, ConvPlan& P) {
+  P = ConvPlan{};
+  P.H = d.height, P.W = d.width, P.KH = d.kernel_h, P.KW = d.kernel_w;
+  P.ph = d.pad_h, P.pw = d.pad_w, P.sh = d.stride_h, P.sw = d.stride_w, P.dh = d.dilation_h, P.dw = d.dilation_w;
+  P.Wo = d.out_w;
+  P.HW = d.height * d.width, P.HoWo = d.out_h * d.out_w;
+  P.Cin = d.channels, P.Cout = d.num_output, P.groups = d.group;
+  P.Cg = d.channels / d.group, P.Ng = d.num_output / d.group;
+  P.M = d.num * P.HoWo;
+  P.Kg = P.Cg * d.kernel_h * d.kernel_w;
+  P.khkw = make_fastdiv(static_cast<uint32_t>(d.kernel_h * d.kernel_w));
+  P.kw_div = make_fastdiv(static_cast<uint32_t>(d.kernel_w));
+  P.howo = make_fastdiv(static_cast<uint32_t>(P.HoWo));
+  P.wo_div = make_fastdiv(static_cast<uint32_t>(d.out_w));
+  P.tiles_p = (P.M + BM - 1) / BM;
+  P.tiles_c = (P.Ng + BN - 1) / BN;
+  P.ksteps = (P.Kg + KS - 1) / KS;
+  P.spt = c.rows / KS;
+  P.ntiles = (P.Kg + c.rows - 1) / c.rows;
+  P.total = (int64_t)d.num * d.num_output * P.HoWo;
+  plan_split(P.ntiles, (int64_t)P.tiles_p * P.tiles_c * P.groups, (size_t)P.total * sizeof(int32_t), split_k, ws_bytes,
+             P.tc, P.split);
+  const Steps st = steps_of(c);
+  P.step = st.step, P.inv_step = st.inv_step, P.qmax = st.qmax, P.dac_xs = st.dac_xs, P.dac_qmax = st.dac_qmax;
+}
+
+size_t conv_part_bytes(const ConvPlan& P) { return P.split > 1 ? (size_t)P.split * P.total * sizeof(int32_t) : 0; }
 
 }  // namespace xb
 }  // namespace
@@ -343,11 +650,7 @@ int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y
   const bool xv = al16(x), wv = al16(w);
 
   const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * xb::A_B;
-  float dac_xs = 1.0f, dac_qmax = 0.0f;
-  if (cfg->dac_bits > 0) {
-    dac_qmax = static_cast<float>((1 << (cfg->dac_bits - 1)) - 1);
-    dac_xs = static_cast<float>(static_cast<double>(cfg->dac_range) / dac_qmax);
-  }
+  const float dac_xs = xb::steps_of(*cfg).dac_xs, dac_qmax = xb::steps_of(*cfg).dac_qmax;
   if (!plan_note("xbar:pack<%s>", xv ? "vec" : "scalar")) {
     char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
     RRAM_REQUIRE(pb != nullptr, "ip_fwd_xbar: packed-activation buffer allocation failed");
@@ -378,7 +681,7 @@ int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y
   }
   if (P.split == 1 || plan_note("xbar:finish")) return RRAM_OK;
   hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s, P.part, P.split, M, N,
-                     P.step, bias, relu, y);
+                     1, P.step, bias, relu, y);
   return launch_status("ip_fwd_xbar finish");
 }
 
@@ -388,6 +691,61 @@ int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, i
   auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
   const int rc = rram_ip_fwd_xbar(ptr(x_align16), ptr(w_align16), nullptr, ptr(1), M, N, K, 0, cfg, 0, split_k,
                                   ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
+  return rc ? rc : rram::copy_text(sc.text, out, cap);
+}
+
+size_t rram_conv2d_fwd_xbar_workspace(const rram_conv_desc* d_in, const rram_xbar_cfg* cfg, int split_k) {
+  if (d_in == nullptr) return 0;
+  rram_conv_desc d = *d_in;
+  if (rram::xb::conv_check(d, cfg, split_k) != RRAM_OK || d.num == 0) return 0;
+  rram::xb::ConvPlan P;
+  rram::xb::make_conv_plan(d, *cfg, split_k, ~static_cast<size_t>(0), P);
+  return rram::xb::conv_part_bytes(P);
+}
+
+int rram_conv2d_fwd_xbar(const rram_conv_desc* d_in, const float* x, const float* w, const float* bias, float* y,
+                         const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
+                         rram_stream_t st) {
+  using namespace rram;
+  RRAM_REQUIRE(d_in != nullptr, "conv2d_fwd_xbar: descriptor is NULL");
+  rram_conv_desc d = *d_in;
+  const int rc0 = xb::conv_check(d, cfg, split_k);
+  if (rc0) return rc0;
+  if (d.num == 0) return RRAM_OK;
+  RRAM_REQUIRE(x && w && y, "conv2d_fwd_xbar: NULL pointer");
+  xb::ConvPlan P;
+  xb::make_conv_plan(d, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
+  RRAM_REQUIRE(P.split == 1 || (ws != nullptr && ws_bytes >= xb::conv_part_bytes(P)),
+               "conv2d_fwd_xbar: workspace of %zu bytes below the %zu of %d splits", ws_bytes, xb::conv_part_bytes(P),
+               P.split);
+  const int64_t wgs = (int64_t)P.tiles_p * P.tiles_c * P.groups * P.split;
+  RRAM_REQUIRE(wgs < (1ll << 31) && (int64_t)P.tiles_p * xb::BM < (1ll << 31), "conv2d_fwd_xbar: grid too large");
+  hipStream_t s = as_stream(st);
+  const bool wv = (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && P.Kg % 4 == 0;
+  P.x = x, P.w = w, P.bias = bias, P.y = y;
+  P.part = P.split > 1 ? static_cast<int32_t*>(ws) : nullptr;
+  P.relu = relu;
+  if (!plan_note("xbar:conv<%s>/s%d", wv ? "vec" : "scalar", P.split)) {
+    const dim3 grid(static_cast<unsigned>(wgs));
+    if (wv)
+      hipLaunchKernelGGL(xb::k_conv_xbar<true>, grid, dim3(256), 0, s, P);
+    else
+      hipLaunchKernelGGL(xb::k_conv_xbar<false>, grid, dim3(256), 0, s, P);
+    const int rc = launch_status("conv2d_fwd_xbar");
+    if (rc) return rc;
+  }
+  if (P.split == 1 || plan_note("xbar:finish")) return RRAM_OK;
+  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks(P.total)), dim3(256), 0, s, P.part, P.split, d.num,
+                     d.num_output, P.HoWo, P.step, bias, relu, y);
+  return launch_status("conv2d_fwd_xbar finish");
+}
+
+int rram_conv2d_fwd_xbar_kernel_ids(const rram_conv_desc* d, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
+                                    int split_k, size_t ws_bytes, char* out, size_t cap) {
+  rram::PlanScope sc;
+  auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
+  const int rc = rram_conv2d_fwd_xbar(d, ptr(x_align16), ptr(w_align16), nullptr, ptr(1), cfg, 0, split_k,
+                                      ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

@@ -137,6 +137,39 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
   }
 }
 
+// crossbar_param { rows adc_bits adc_range [dac_bits dac_range] }, or the Net
+// options `crossbar` (InnerProduct) / `crossbar_conv` (Convolution)
+// ("rows,adc_bits,adc_range[,dac_bits,dac_range]", handed down as
+// rram_crossbar to layers without the message).  False: neither is set.
+static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c) {
+  const Msg* xp = lp.sub("crossbar_param");
+  if (xp == nullptr && !lp.has("rram_crossbar")) return false;
+  *c = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
+  if (xp != nullptr) {
+    c->rows = static_cast<int32_t>(xp->integer("rows", 0));
+    c->adc_bits = static_cast<int32_t>(xp->integer("adc_bits", 0));
+    c->adc_range = static_cast<float>(xp->num("adc_range", 0.0));
+    c->dac_bits = static_cast<int32_t>(xp->integer("dac_bits", 0));
+    c->dac_range = static_cast<float>(xp->num("dac_range", 1.0));
+    return true;
+  }
+  std::vector<double> v;
+  std::stringstream ss(lp.str("rram_crossbar"));
+  std::string t;
+  try {
+    while (std::getline(ss, t, ',')) v.push_back(std::stod(t));
+  } catch (const std::exception&) {
+    v.clear();
+  }
+  CAFFE_CHECK(v.size() == 3 || v.size() == 5, name << ": option crossbar wants "
+                                                   << "rows,adc_bits,adc_range[,dac_bits,dac_range]");
+  c->rows = static_cast<int32_t>(v[0]);
+  c->adc_bits = static_cast<int32_t>(v[1]);
+  c->adc_range = static_cast<float>(v[2]);
+  if (v.size() == 5) c->dac_bits = static_cast<int32_t>(v[3]), c->dac_range = static_cast<float>(v[4]);
+  return true;
+}
+
 // ★ ------------------------------------------------------- Convolution
 template <typename Dtype>
 void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom,
@@ -155,6 +188,16 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom
   CAFFE_CHECK(desc_.channels % desc_.group == 0 && desc_.num_output % desc_.group == 0,
               "Convolution: channels/num_output must be divisible by group");
   bias_term_ = cp.boolean("bias_term", true);
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_);
+  if (xbar_on_) {
+    // the kernel library's own checks of the configuration, on a host-only plan
+    // query for one image (before any blob is allocated: no device is touched)
+    rram_conv_desc d = desc_;
+    d.num = 1, d.height = bottom[0]->shape(2), d.width = bottom[0]->shape(3);
+    char id[8];
+    CAFFE_CHECK(rram_conv2d_fwd_xbar_kernel_ids(&d, &xbar_, 1, 1, 0, 0, id, sizeof id) > 0,
+                this->name() << ": crossbar_param: " << rram_last_error());
+  }
   this->blobs_.clear();
   this->blobs_.push_back(std::make_shared<Blob<Dtype>>(
       std::vector<int>{desc_.num_output, desc_.channels / desc_.group, kh, kw}));
@@ -178,7 +221,7 @@ void ConvolutionLayer<Dtype>::Reshape(const std::vector<Blob<Dtype>*>& bottom,
   top[0]->Reshape({desc_.num, desc_.num_output, desc_.out_h, desc_.out_w});
   const int eng = rram_get_f32_engine();
   if (desc_.num != oct_key_[0] || desc_.height != oct_key_[1] || desc_.width != oct_key_[2] || eng != oct_key_[3]) {
-    want_in_oct_ = rram_conv_input_octets(&desc_) == 1;
+    want_in_oct_ = !xbar_on_ && rram_conv_input_octets(&desc_) == 1;
     oct_key_[0] = desc_.num;
     oct_key_[1] = desc_.height;
     oct_key_[2] = desc_.width;
@@ -233,6 +276,18 @@ template <typename Dtype>
 void ConvolutionLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bottom,
                                           const std::vector<Blob<Dtype>*>& top) {
   CAFFE_CHECK(bottom[0] != top[0], this->name() << ": in-place convolution is not allowed");
+  if (xbar_on_) {
+    // the crossbar read-out of the fp32 bottom over the whole batch (batch-invariant
+    // per image, so map groups need no loop); no companion, no weight pack
+    CAFFE_CHECK(!bottom[0]->data()->fp32_stale,
+                this->name() << ": fp32 input unwritten (its producer wrote only the octet companion)");
+    void* ws = Caffe::workspace(rram_conv2d_fwd_xbar_workspace(&desc_, &xbar_, 0) + 256);
+    RRAM_CALL(rram_conv2d_fwd_xbar(&desc_, bottom[0]->gpu_data(), this->blobs_[0]->gpu_data(),
+                                   bias_term_ ? this->blobs_[1]->gpu_data() : nullptr, top[0]->mutable_gpu_data(),
+                                   &xbar_, fused_relu ? 1 : 0, 0, ws, Caffe::workspace_size(), Caffe::stream()));
+    top[0]->data()->fp32_stale = false;
+    return;
+  }
   // map groups: plan the fp32 engine's split-K for one group's images (restored on every exit)
   struct PlanNum {
     const bool on;
@@ -376,35 +431,8 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
     FillBlob(this->blobs_[1].get(), ip.sub_or_empty("bias_filler"), seed, 1);
   }
   this->param_propagate_down_.assign(this->blobs_.size(), true);
-  // crossbar_param { rows adc_bits adc_range [dac_bits dac_range] }, or the Net
-  // option `crossbar` ("rows,adc_bits,adc_range[,dac_bits,dac_range]", handed
-  // down as rram_crossbar to layers without the message)
-  const Msg* xp = this->layer_param_.sub("crossbar_param");
-  xbar_on_ = xp != nullptr || this->layer_param_.has("rram_crossbar");
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_);
   if (xbar_on_) {
-    xbar_ = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
-    if (xp != nullptr) {
-      xbar_.rows = static_cast<int32_t>(xp->integer("rows", 0));
-      xbar_.adc_bits = static_cast<int32_t>(xp->integer("adc_bits", 0));
-      xbar_.adc_range = static_cast<float>(xp->num("adc_range", 0.0));
-      xbar_.dac_bits = static_cast<int32_t>(xp->integer("dac_bits", 0));
-      xbar_.dac_range = static_cast<float>(xp->num("dac_range", 1.0));
-    } else {
-      std::vector<double> v;
-      std::stringstream ss(this->layer_param_.str("rram_crossbar"));
-      std::string t;
-      try {
-        while (std::getline(ss, t, ',')) v.push_back(std::stod(t));
-      } catch (const std::exception&) {
-        v.clear();
-      }
-      CAFFE_CHECK(v.size() == 3 || v.size() == 5, this->name() << ": option crossbar wants "
-                                                               << "rows,adc_bits,adc_range[,dac_bits,dac_range]");
-      xbar_.rows = static_cast<int32_t>(v[0]);
-      xbar_.adc_bits = static_cast<int32_t>(v[1]);
-      xbar_.adc_range = static_cast<float>(v[2]);
-      if (v.size() == 5) xbar_.dac_bits = static_cast<int32_t>(v[3]), xbar_.dac_range = static_cast<float>(v[4]);
-    }
     // the kernel library's own checks of the configuration, on a host-only plan query
     CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
     char id[8];

@@ -27,7 +27,7 @@ class ConvolutionLayer : public Layer<Dtype> {
   bool cache_wpack = false;
   const rram_conv_desc& desc() const { return desc_; }
   bool input_octets_now(const Blob<Dtype>* bottom) const override {
-    if (bottom->num_axes() != 4) return false;
+    if (bottom->num_axes() != 4 || xbar_on_) return false;
     rram_conv_desc d = desc_;
     d.num = bottom->shape(0);
     d.height = bottom->shape(2);
@@ -35,6 +35,7 @@ class ConvolutionLayer : public Layer<Dtype> {
     return bottom->shape(1) == d.channels && rram_conv_input_octets(&d) == 1;
   }
   bool write_into_concat(Blob<Dtype>* concat_top, int channel_offset) override {
+    if (xbar_on_) return false;  // the crossbar read-out writes its own dense top
     concat_top_ = concat_top;
     concat_off_ = channel_offset;
     return true;
@@ -55,6 +56,7 @@ class ConvolutionLayer : public Layer<Dtype> {
     return true;
   }
   bool set_octet_reader(Layer<Dtype>* reader) override {
+    if (xbar_on_) return false;  // the crossbar read-out writes no companion
     if (reader != nullptr && (this->phase_ != TEST || concat_top_ != nullptr)) return false;
     octet_reader_ = reader;
     return true;
@@ -74,6 +76,12 @@ class ConvolutionLayer : public Layer<Dtype> {
   Layer<Dtype>* octet_reader_ = nullptr;  // convolution-output fold: the top's only reader
   int groups_ = 1;                        // set_map_groups
   bool flip_ok_ = false;
+  // crossbar_param (or the Net option `crossbar_conv`): the forward is the
+  // crossbar-tiled ADC read-out (rram_conv2d_fwd_xbar) of the fp32 bottom over
+  // the whole batch: no octet companion read or written, no weight pack, no
+  // Concat or octet fold; the backward unchanged (straight-through)
+  bool xbar_on_ = false;
+  rram_xbar_cfg xbar_{};
 };
 
 // ★ InnerProduct (inner_product_layer.cpp:9-141, .cu:9-75).

@@ -191,6 +191,9 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
     // option crossbar: every InnerProduct layer without a crossbar_param of its own
     if (type == "InnerProduct" && options.has("crossbar") && lp.sub("crossbar_param") == nullptr)
       lp.set("rram_crossbar", options.str("crossbar"));
+    // option crossbar_conv: the same for every Convolution layer
+    if (type == "Convolution" && options.has("crossbar_conv") && lp.sub("crossbar_param") == nullptr)
+      lp.set("rram_crossbar", options.str("crossbar_conv"));
     auto layer = LayerRegistry<Dtype>::CreateLayer(lp);
     layer->layer_id = static_cast<uint32_t>(lid);
     const std::string lname = lp.str("name");

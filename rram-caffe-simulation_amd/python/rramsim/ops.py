@@ -460,6 +460,23 @@ def ip_fwd_xbar_kernel_ids(M, N, K_, cfg, x_align16=True, w_align16=True, split_
                      split_k, int(ws_bytes))
 
 
+def conv_fwd_xbar(d, x, w, bias, y, cfg, relu=False, split_k=0, workspace=None):
+    """rram_conv2d_fwd_xbar: y = the ADC read-out of conv(x, w) from crossbars of cfg.rows rows of the
+    unrolled kernel (d: a conv_desc; split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_conv2d_fwd_xbar(C.byref(d), _p(x), _p(w), _p(bias), _p(y), C.byref(cfg), int(relu), split_k,
+                                        _p(workspace), wsb, _stream()), "conv2d_fwd_xbar")
+
+
+def conv_fwd_xbar_workspace(d, cfg, split_k=0):
+    return _lib().rram_conv2d_fwd_xbar_workspace(C.byref(d), C.byref(cfg), split_k)
+
+
+def conv_fwd_xbar_kernel_ids(d, cfg, x_align16=True, w_align16=True, split_k=0, ws_bytes=0):
+    return _id_lines(_lib().rram_conv2d_fwd_xbar_kernel_ids, C.byref(d), C.byref(cfg), int(x_align16),
+                     int(w_align16), split_k, int(ws_bytes))
+
+
 def ip_rows_pack_bytes(M, N, K_, ws_bytes):
     """(bytes, rows per tile) of the bf16x6 engine's packed-row input form (0, 0: not served)."""
     bmc = C.c_int(0)

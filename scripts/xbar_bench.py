@@ -1,9 +1,12 @@
-"""Times rram_ip_fwd_xbar beside rram_ip_fwd (the same MFMA count without the
-per-tile rounding) on the fc6 / fc7 / CIFAR ip1 shapes: call times from device
-events (pack, GEMM and finish / split-K reduce included), the two alternated
-in one process, the median and range of REPS windows of ITERS calls each.
+"""Times the crossbar-tiled forwards beside the plain forwards of the same
+shapes (the same MFMA count without the per-tile rounding): rram_ip_fwd_xbar
+beside rram_ip_fwd on the fc6 / fc7 / CIFAR ip1 shapes, or with --conv
+rram_conv2d_fwd_xbar beside rram_conv2d_fwd on AlexNet conv2 / conv3, VGG11
+conv2 / conv8 and a GoogLeNet 1x1.  Call times from device events (every launch
+of the call included), the two alternated in one process, the median and range
+of REPS windows of ITERS calls each.
 
-    python scripts/xbar_bench.py [out.txt]
+    python scripts/xbar_bench.py [--conv] [out.txt]
 """
 import sys
 from pathlib import Path
@@ -17,6 +20,12 @@ from rramsim import ops  # noqa: E402
 
 ROOF = 2.5e15 / 6          # bf16 dense peak over the six products, FLOP/s of fp32-equivalent work
 SHAPES = [("fc6", 256, 4096, 9216, 128, 8), ("fc7", 256, 4096, 4096, 128, 8), ("cifar ip1", 100, 64, 1024, 64, 8)]
+# name, x shape, Cout, kernel, pad, group, R, B
+CONVS = [("alexnet conv2 b256", (256, 96, 27, 27), 256, 5, 2, 2, 128, 8),
+         ("alexnet conv3 b256", (256, 256, 13, 13), 384, 3, 1, 1, 128, 8),
+         ("vgg11 conv2 b100", (100, 64, 16, 16), 128, 3, 1, 1, 128, 8),
+         ("vgg11 conv8 b100", (100, 512, 2, 2), 512, 3, 1, 1, 128, 8),
+         ("googlenet 3a 1x1 b128", (128, 192, 28, 28), 64, 1, 0, 1, 128, 8)]
 ITERS, REPS = 50, 7
 
 
@@ -30,8 +39,22 @@ def window(fn):
     return a.elapsed_time(b) / ITERS * 1e3   # us per call
 
 
-def main():
-    assert torch.cuda.is_available(), "needs a GPU"
+def row(head, fx, fp, idx, idp, flops):
+    """One result line: fx (crossbar) and fp (plain) warmed up, then timed in alternating windows."""
+    for f in (fx, fp):
+        for _ in range(5):
+            f()
+    torch.cuda.synchronize()
+    tx, tp = [], []
+    for _ in range(REPS):
+        tx.append(window(fx))
+        tp.append(window(fp))
+    mx, mp = sorted(tx)[REPS // 2], sorted(tp)[REPS // 2]
+    return (f"{head} | {mx:.1f} ({min(tx):.1f}..{max(tx):.1f}) {','.join(idx)} | "
+            f"{mp:.1f} ({min(tp):.1f}..{max(tp):.1f}) {','.join(idp)} | {mx / mp:.2f} | {flops / (mx * 1e-6) / ROOF:.3f}")
+
+
+def ip_rows():
     lines = ["shape  M x N x K  R B | xbar us (min..max) ids | plain us (min..max) ids | ratio | xbar share of 416.7 TFLOP/s"]
     for name, M, N, K, R, B in SHAPES:
         g = torch.Generator(device="cuda").manual_seed(1)
@@ -44,24 +67,40 @@ def main():
         wsp = torch.empty(min(16 * M * N * 4, 256 << 20), dtype=torch.uint8, device="cuda")
         fx = lambda: ops.ip_fwd_xbar(x, w, bias, y, M, N, K, cfg, relu=True, workspace=wsx)  # noqa: E731
         fp = lambda: ops.ip_fwd(x, w, bias, y, M, N, K, relu=True, workspace=wsp)            # noqa: E731
-        for f in (fx, fp):
-            for _ in range(5):
-                f()
-        torch.cuda.synchronize()
-        tx, tp = [], []
-        for _ in range(REPS):
-            tx.append(window(fx))
-            tp.append(window(fp))
-        mx, mp = sorted(tx)[REPS // 2], sorted(tp)[REPS // 2]
-        idx = ",".join(ops.ip_fwd_xbar_kernel_ids(M, N, K, cfg, ws_bytes=wsx.numel()))
-        idp = ",".join(ops.ip_fwd_kernel_ids(M, N, K, relu=True, ws_bytes=wsp.numel()))
-        lines.append(f"{name}  {M} x {N} x {K}  {R} {B} | {mx:.1f} ({min(tx):.1f}..{max(tx):.1f}) {idx} | "
-                     f"{mp:.1f} ({min(tp):.1f}..{max(tp):.1f}) {idp} | {mx / mp:.2f} | "
-                     f"{2.0 * M * N * K / (mx * 1e-6) / ROOF:.3f}")
-    text = "\n".join(lines) + "\n"
+        lines.append(row(f"{name}  {M} x {N} x {K}  {R} {B}", fx, fp,
+                         ops.ip_fwd_xbar_kernel_ids(M, N, K, cfg, ws_bytes=wsx.numel()),
+                         ops.ip_fwd_kernel_ids(M, N, K, relu=True, ws_bytes=wsp.numel()), 2.0 * M * N * K))
+    return lines
+
+
+def conv_rows():
+    lines = ["shape  x -> Cout k/pad/group  R B | xbar us (min..max) ids | plain us (min..max) ids | ratio | "
+             "xbar share of 416.7 TFLOP/s"]
+    for name, xs, cout, k, pad, group, R, B in CONVS:
+        d = ops.conv_desc(xs, cout, k, 1, pad, 1, group)
+        kg = xs[1] // group * k * k
+        g = torch.Generator(device="cuda").manual_seed(1)
+        x = torch.randn(*xs, device="cuda", generator=g)
+        w = torch.randn(cout, xs[1] // group, k, k, device="cuda", generator=g) * kg ** -0.5
+        bias = torch.randn(cout, device="cuda", generator=g)
+        y = torch.empty(xs[0], cout, d.out_h, d.out_w, device="cuda")
+        cfg = ops.xbar_cfg(R, B, 4.0)
+        wsx = torch.empty(max(1, ops.conv_fwd_xbar_workspace(d, cfg)), dtype=torch.uint8, device="cuda")
+        fx = lambda: ops.conv_fwd_xbar(d, x, w, bias, y, cfg, relu=True, workspace=wsx)      # noqa: E731
+        fp = lambda: ops.conv2d_fwd(d, x, w, bias, y, relu=True)                             # noqa: E731
+        lines.append(row(f"{name}  {'x'.join(map(str, xs))} -> {cout} {k}/{pad}/{group}  {R} {B}", fx, fp,
+                         ops.conv_fwd_xbar_kernel_ids(d, cfg, ws_bytes=wsx.numel()), ops.conv_fwd_kernel_ids(d),
+                         2.0 * xs[0] * d.out_h * d.out_w * cout * kg))
+    return lines
+
+
+def main():
+    assert torch.cuda.is_available(), "needs a GPU"
+    args = [a for a in sys.argv[1:] if a != "--conv"]
+    text = "\n".join(conv_rows() if "--conv" in sys.argv[1:] else ip_rows()) + "\n"
     print(text, end="")
-    if len(sys.argv) > 1:
-        Path(sys.argv[1]).write_text(text)
+    if args:
+        Path(args[0]).write_text(text)
 
 
 if __name__ == "__main__":
