@@ -698,6 +698,38 @@ int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y
 size_t rram_ip_fwd_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
 int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                 int split_k, size_t ws_bytes, char* out, size_t cap);
+/* The bit-serial read-out of the same arrays (no reference counterpart; DESIGN
+ * §7.6): the input is streamed one bit per cycle, the ADC converts the column
+ * sum of every bit plane of every tile on its own, and a shift-and-add
+ * combines the codes.  The DAC is mandatory: cmax = 2^(dac_bits-1) - 1,
+ * xs = dac_range / cmax, c = clamp(rint(x / xs), +-cmax) (an integer), plane
+ * j = 0 .. dac_bits-2 is u_j = sign(c) * ((|c| >> j) & 1) in {-1, 0, +1}
+ * (sign-magnitude).  Per tile t and plane j, p_{t,j} = sum u_j[m][k] W[n][k]
+ * in fp32 from zero (three exact bf16 products per weight, smallest term
+ * first), q_{t,j} = clamp(rint(p_{t,j} / step), +-qmax) with qmax and step as
+ * above, S = sum_t sum_j 2^j q_{t,j} as int32, and
+ *   y = float(S) * out_scale + bias, ReLU;  out_scale = float(step * xs) (in double).
+ * adc_range is therefore the full scale of ONE PLANE's column sum, in weight
+ * units (a sum of +-W over the tile's rows), not the x * w unit of
+ * rram_ip_fwd_xbar.
+ * Refused (RRAM_EINVAL before the device is touched): everything
+ * rram_ip_fwd_xbar refuses, dac_bits == 0, and ceil(K / rows) * qmax * cmax >=
+ * 2^31 (below that S and every partial slab fit int32).  M == 0 or N == 0 is
+ * RRAM_OK with no launch.
+ * Planes beyond 7 are cut into C = ceil((dac_bits - 1) / 7) chunks, a further
+ * factor of the grid beside the S splits over K: with S * C > 1 the int32
+ * slabs need S * C * M * N * 4 bytes of workspace
+ * (rram_ip_fwd_xbar_bs_workspace; split_k = 0: the most the planner would
+ * use), else RRAM_EINVAL.  S is an integer: every split and every chunking
+ * give the same bits.  rram_ip_fwd_xbar_bs_kernel_ids (host only):
+ * xbar:pack_codes<vec|scalar>, xbar:ip_bs<vec|scalar;pPC>/sS/cC (PC planes per
+ * chunk: 4 up to 4 planes, else 7), and xbar:finish when S * C > 1. */
+int rram_ip_fwd_xbar_bs(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
+                        rram_stream_t stream);
+size_t rram_ip_fwd_xbar_bs_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
+int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
+                                   int split_k, size_t ws_bytes, char* out, size_t cap);
 /* The crossbar-tiled Convolution forward (no reference counterpart; DESIGN
  * §7.5): the array of group g holds the unrolled kernel, rows
  * k = (ci * kernel_h + i) * kernel_w + j (Caffe's im2col / weight-blob order),

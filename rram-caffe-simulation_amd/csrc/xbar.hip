@@ -29,6 +29,8 @@
 //
 // The crossbar-tiled Convolution forward (k_conv_xbar) is the same
 // array with the unrolled kernel as its rows: see the comment above the kernel.
+// The bit-serial read-out of the InnerProduct array (k_ip_xbar_bs)
+// converts every input bit plane on its own: see the comment above that kernel.
 #include <algorithm>
 #include <cmath>
 
@@ -250,6 +252,264 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   int32_t* part = P.split > 1 ? P.part + (int64_t)z * P.M * P.N : nullptr;
 #pragma unroll
   for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + 32 * i + 8 * (r >> 2) + 4 * lh + (r & 3);
+      if (m >= P.M) continue;
+      if (part != nullptr)
+        part[(int64_t)m * P.N + n] = S[i][r];
+      else
+        P.y[(int64_t)m * P.N + n] = xbar_out(S[i][r], P.step, P.bias, n, P.relu);
+    }
+}
+
+// The bit-serial read-out: the DAC code c of every activation is
+// streamed one magnitude bit per cycle, plane j holding u_j = sign(c) *
+// ((|c| >> j) & 1) in {-1, 0, +1}; the ADC converts every plane's column sum of
+// every crossbar tile on its own and a shift-and-add combines the codes:
+//   S[m][n] = sum_t sum_j 2^j q_{t,j}[m][n] (int32),  y = float(S) * out_scale + bias.
+// A plane is one exact bf16 term, so a product with a weight is three MFMAs
+// (u * w_l, u * w_m, u * w_h), and one split weight fragment serves every plane.
+//
+// Activations.  k_xbar_pack_codes writes the 16-bit sign-magnitude code (bit 15
+// the sign, bits 0..14 |c|) of every activation, in the LDS image of a K-step:
+// [row tile][K-step of 32][bm rows][80 B], a row = four 16-byte units (group g,
+// half h: the 8 codes k = 16 h + 8 g + j) + 16 B pad (5 units: conflict-free
+// ds_read_b128).  No plane exists in memory: a lane forms plane j of its 8
+// codes in registers from the one 16-byte read.
+//
+// Work split.  A workgroup (4 waves) owns 32 MI rows x 128 columns for a range
+// of whole crossbar tiles and one chunk of up to PC planes; wave w owns all
+// rows x columns 32 w .. 32 w + 31: MI blocks, each with PC fp32 sets (one per
+// plane of the chunk) and one int32 set S.  At a tile boundary the ADC runs on
+// every plane's set in registers, the code shifted by the plane index goes to
+// S and the sets are cleared.  <PC 7, MI 2> serves up to 7 planes in one pass
+// (dac_bits <= 8), <PC 4, MI 2> up to 4 planes in half the registers (MI 4
+// spills: DESIGN §7.6); more than 7 planes are cut into chunks of 7, a further factor of
+// the grid beside the K splits (the sum is an integer, so chunks combine like
+// splits: slabs [chunk][split][M][N] and k_xbar_finish).  The weight staging
+// and the two-stage pipeline are k_ip_xbar's.
+constexpr int CRB = 64 + 16;  // code row bytes per K-step
+
+template <int MI_>
+struct Bs {
+  static constexpr int BM = 32 * MI_;
+  static constexpr int A_B = BM * CRB;  // code bytes per K-step and row tile
+  static constexpr int A_U = A_B / 16;
+  static constexpr int A_LD = (A_U + 255) / 256;
+  static constexpr int STAGE = A_B + B_B;
+};
+
+struct BsPlan : Plan {  // Plan::step is out_scale = step * xs
+  int planes;           // dac_bits - 1
+  int pc, chunks;       // planes per chunk, ceil(planes / pc)
+  int bm;               // rows of a workgroup tile
+};
+
+// x [M][K] fp32 -> 16-bit sign-magnitude DAC codes clamp(rint(x / xs), +-cmax)
+// in the K-step slabs k_ip_xbar_bs copies to LDS (zero past M and K, zero
+// pad).  One thread per (row, K-step, group, half): 8 activations in, 16 bytes out.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_xbar_pack_codes(const float* __restrict__ x, int M, int K,
+                                                         char* __restrict__ out, int ksteps, int bm, int64_t units,
+                                                         float xs, float cmax) {
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    const int h = static_cast<int>(u & 1), g = static_cast<int>((u >> 1) & 1);
+    const int64_t r = u >> 2;
+    const int ks = static_cast<int>(r % ksteps);
+    const int64_t mrow = r / ksteps;  // tm * bm + row
+    const int k = ks * KS + 16 * h + 8 * g;
+    float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (mrow < M) {
+      const float* src = x + mrow * K + k;
+      if (VEC) {  // K % 4 == 0, x 16-byte aligned
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          if (k + 4 * q < K) {
+            const float4 f = *reinterpret_cast<const float4*>(src + 4 * q);
+            v[4 * q] = f.x, v[4 * q + 1] = f.y, v[4 * q + 2] = f.z, v[4 * q + 3] = f.w;
+          }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (k + j < K) v[j] = src[j];
+      }
+    }
+    uint32_t cw[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      uint32_t c2[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float c = __builtin_amdgcn_fmed3f(__builtin_rintf(v[2 * p + e] / xs), -cmax, cmax);
+        c2[e] = static_cast<uint32_t>(__builtin_fabsf(c)) | (c < 0.0f ? 0x8000u : 0u);
+      }
+      cw[p] = c2[0] | c2[1] << 16;
+    }
+    const int64_t tm = mrow / bm;
+    const int row = static_cast<int>(mrow - tm * bm);
+    char* rowp = out + ((tm * ksteps + ks) * bm + row) * CRB;
+    *reinterpret_cast<uint4*>(rowp + (g * 2 + h) * 16) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+    if (g == 1 && h == 1) *reinterpret_cast<uint4*>(rowp + 64) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+template <bool VEC, int PC, int MI_>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_ip_xbar_bs(BsPlan P) {
+  typedef Bs<MI_> T;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) char smem[2 * T::STAGE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const int id = xcd_tile_id(blockIdx.x, gridDim.x);
+  const int tm = __builtin_amdgcn_readfirstlane(id % P.tiles_m);
+  const int tn = __builtin_amdgcn_readfirstlane((id / P.tiles_m) % P.tiles_n);
+  const int zc = __builtin_amdgcn_readfirstlane(id / (P.tiles_m * P.tiles_n));  // chunk * split + z: the slab
+  const int z = zc % P.split;
+  const int j0 = (zc / P.split) * PC;          // the chunk's first plane
+  const int np = min(PC, P.planes - j0);       // ... and how many it has
+  const int m0 = tm * T::BM, n0 = tn * BN;
+  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
+  const int s0 = t0 * P.spt, s1 = min(P.ksteps, t1 * P.spt);
+
+  // this thread's pieces of a K-step: A_LD 16-byte units of the codes, B_LD
+  // quads (row, 4 k) of the weights
+  const char* asrc = P.apack + (int64_t)tm * P.ksteps * T::A_B + tid * 16;
+  const float* bsrc[B_LD];
+  int bq[B_LD], blds[B_LD];
+#pragma unroll
+  for (int i = 0; i < B_LD; ++i) {
+    const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
+    bsrc[i] = n0 + row < P.N ? P.w + (int64_t)(n0 + row) * P.K + 4 * q : nullptr;
+    bq[i] = 4 * q;
+    blds[i] = T::A_B + row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4);
+  }
+  uint4 ra[T::A_LD];
+  float4 rb[B_LD];
+  auto gload = [&](int s) {
+    const char* a = asrc + (int64_t)s * T::A_B;
+#pragma unroll
+    for (int i = 0; i < T::A_LD; ++i)
+      if (tid + 256 * i < T::A_U) ra[i] = *reinterpret_cast<const uint4*>(a + 4096 * i);
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+      const int k = s * KS + bq[i];
+      float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (bsrc[i] != nullptr) {
+        const float* p = bsrc[i] + s * KS;
+        if (VEC) {  // K % 4 == 0, w 16-byte aligned
+          if (k < P.K) f = *reinterpret_cast<const float4*>(p);
+        } else {
+          if (k < P.K) f.x = p[0];
+          if (k + 1 < P.K) f.y = p[1];
+          if (k + 2 < P.K) f.z = p[2];
+          if (k + 3 < P.K) f.w = p[3];
+        }
+      }
+      rb[i] = f;
+    }
+  };
+  auto lstore = [&](char* st) {
+#pragma unroll
+    for (int i = 0; i < T::A_LD; ++i)
+      if (tid + 256 * i < T::A_U) *reinterpret_cast<uint4*>(st + tid * 16 + 4096 * i) = ra[i];
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4*>(st + blds[i]) = rb[i];
+  };
+
+  // a cleared set comes out of the matrix pipe (0 * 0 + 0, the addend an inline
+  // constant): zeros written as vector registers would be copied in set by set,
+  // PC * MI * 16 more registers live at every tile boundary
+  auto zero_set = [&]() {
+    const x6::bf16x8 z = __builtin_bit_cast(x6::bf16x8, u32x4{0u, 0u, 0u, 0u});
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(z, z, floatx16{}, 0, 0, 0);
+  };
+  floatx16 acc[MI_][PC];  // the current crossbar tile's partial sums, one set per plane
+  int32_t S[MI_][16];     // the shift-and-add of the ADC codes
+#pragma unroll
+  for (int i = 0; i < MI_; ++i) {
+#pragma unroll
+    for (int j = 0; j < PC; ++j) acc[i][j] = zero_set();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S[i][r] = 0;
+  }
+
+  const int nw = 32 * wave + lr;  // this lane's weight row (output column) inside the tile
+  auto compute = [&](const char* st) {
+    const float* sb = reinterpret_cast<const float*>(st + T::A_B) + nw * KS;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      float b[8];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
+        b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
+      }
+      x6::Parts wp;
+      x6::split8_safe(b, wp);
+#pragma unroll
+      for (int i = 0; i < MI_; ++i) {
+        // 8 codes as 4 packed pairs; plane j of a pair is bit j of each half as the
+        // bf16 1.0 (0x3F80 = (1 << 14) - (1 << 7)) under the pair's sign bits
+        const u32x4 cw = *reinterpret_cast<const u32x4*>(st + (i * 32 + lr) * CRB + (g * 2 + lh) * 16);
+        const u32x4 sg = cw & 0x80008000u;
+#pragma unroll
+        for (int j = 0; j < PC; ++j)
+          if (j < np) {
+            const u32x4 bits = (cw >> static_cast<uint32_t>(j0 + j)) & 0x00010001u;
+            const x6::bf16x8 u = __builtin_bit_cast(x6::bf16x8, ((bits << 14) - (bits << 7)) | sg);
+            floatx16 c = acc[i][j];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u, wp.l, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u, wp.m, c, 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u, wp.h, c, 0, 0, 0);
+          }
+      }
+    }
+  };
+  // the ADC at a tile boundary, per plane: codes shifted by the plane index into S, the sets cleared
+  auto adc = [&]() {
+#pragma unroll
+    for (int i = 0; i < MI_; ++i)
+#pragma unroll
+      for (int j = 0; j < PC; ++j) {
+        // every set of the pass is converted (a plane past np has stayed 0 and adds
+        // 0): per-plane branches here make the sets merge values, copied out all at once
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float q =
+              __builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(acc[i][j][r], P.inv_step)), -P.qmax, P.qmax);
+          S[i][r] += static_cast<int32_t>(q) * (1 << (j0 + j));
+        }
+        acc[i][j] = zero_set();
+      }
+  };
+
+  gload(s0);
+  lstore(smem);
+  __syncthreads();
+  // two levels, crossbar tiles then their K-steps (the last tile may be short),
+  // so that the ADC sits between loops and the sets stay in place
+  for (int s = s0; s < s1;) {
+    const int se = min(s1, s + P.spt);
+    for (; s < se; ++s) {
+      const int cur = (s - s0) & 1;
+      const bool more = s + 1 < s1;
+      if (more) gload(s + 1);
+      compute(smem + cur * T::STAGE);
+      if (more) lstore(smem + (cur ^ 1) * T::STAGE);
+      __syncthreads();
+    }
+    adc();
+  }
+
+  // lane (lr, lh) holds column lr, rows 32 i + 8 (r >> 2) + 4 lh + (r & 3)
+  const int n = n0 + nw;
+  if (n >= P.N) return;
+  int32_t* part = P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr;
+#pragma unroll
+  for (int i = 0; i < MI_; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + 32 * i + 8 * (r >> 2) + 4 * lh + (r & 3);
@@ -576,6 +836,54 @@ void make_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t 
 
 size_t part_bytes(const Plan& P) { return P.split > 1 ? (size_t)P.split * P.M * P.N * sizeof(int32_t) : 0; }
 
+// The bit-serial read-out's checks (host only) and plan.  The DAC is mandatory,
+// and S (so every partial slab too) must fit int32: |S| <= ntiles * qmax * cmax.
+int bs_check(int M, int N, int K, const rram_xbar_cfg* c, int transpose) {
+  const int rc = check(M, N, K, c, transpose);
+  if (rc) return rc;
+  RRAM_REQUIRE(c->dac_bits != 0, "ip_fwd_xbar_bs: bit-serial inputs need a DAC (dac_bits in [2, 16])");
+  const int64_t ntiles = (K + c->rows - 1) / c->rows;
+  const int64_t qmax = (1 << (c->adc_bits - 1)) - 1, cmax = (1 << (c->dac_bits - 1)) - 1;
+  RRAM_REQUIRE(ntiles * qmax * cmax < (1ll << 31), "ip_fwd_xbar_bs: %lld tiles x qmax %lld x cmax %lld overflows int32",
+               (long long)ntiles, (long long)qmax, (long long)cmax);
+  return RRAM_OK;
+}
+
+// up to 4 planes: <PC 4, MI 2>; else chunks of 7 planes on <PC 7, MI 2> (both
+// 64-row tiles).  The chunk count is folded into the planner's
+// workgroup count and slab size, so a multi-chunk problem asks for fewer K splits.
+void make_bs_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t ws_bytes, BsPlan& P) {
+  P = BsPlan{};
+  P.M = M, P.N = N, P.K = K;
+  P.planes = c.dac_bits - 1;
+  P.pc = P.planes <= 4 ? 4 : 7;
+  P.chunks = (P.planes + P.pc - 1) / P.pc;
+  P.bm = Bs<2>::BM;
+  P.tiles_m = (M + P.bm - 1) / P.bm;
+  P.tiles_n = (N + BN - 1) / BN;
+  P.ksteps = (K + KS - 1) / KS;
+  P.spt = c.rows / KS;
+  P.ntiles = (K + c.rows - 1) / c.rows;
+  plan_split(P.ntiles, (int64_t)P.tiles_m * P.tiles_n * P.chunks, (size_t)M * N * sizeof(int32_t) * P.chunks, split_k,
+             ws_bytes, P.tc, P.split);
+  const Steps st = steps_of(c);
+  const int qmax = (1 << (c.adc_bits - 1)) - 1, cmax = (1 << (c.dac_bits - 1)) - 1;
+  P.step = static_cast<float>(static_cast<double>(c.adc_range) / qmax * (static_cast<double>(c.dac_range) / cmax));
+  P.inv_step = st.inv_step, P.qmax = st.qmax;
+}
+
+size_t bs_part_bytes(const BsPlan& P) {
+  return P.split * P.chunks > 1 ? (size_t)P.split * P.chunks * P.M * P.N * sizeof(int32_t) : 0;
+}
+
+template <bool VEC>
+void launch_bs(const BsPlan& P, dim3 grid, hipStream_t s) {
+  if (P.pc == 4)
+    hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 4, 2>), grid, dim3(256), 0, s, P);
+  else
+    hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 7, 2>), grid, dim3(256), 0, s, P);
+}
+
 // The convolution's checks (host only; d gets its output shape) and plan.
 int conv_check(rram_conv_desc& d, const rram_xbar_cfg* c, int split_k) {
   const int rc0 = check_cfg(c, "conv2d_fwd_xbar");
@@ -691,6 +999,78 @@ int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, i
   auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
   const int rc = rram_ip_fwd_xbar(ptr(x_align16), ptr(w_align16), nullptr, ptr(1), M, N, K, 0, cfg, 0, split_k,
                                   ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
+  return rc ? rc : rram::copy_text(sc.text, out, cap);
+}
+
+size_t rram_ip_fwd_xbar_bs_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k) {
+  if (rram::xb::bs_check(M, N, K, cfg, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
+  rram::xb::BsPlan P;
+  rram::xb::make_bs_plan(M, N, K, *cfg, split_k, ~static_cast<size_t>(0), P);
+  return rram::xb::bs_part_bytes(P);
+}
+
+int rram_ip_fwd_xbar_bs(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
+                        rram_stream_t st) {
+  using namespace rram;
+  const int rc0 = xb::bs_check(M, N, K, cfg, transpose);
+  if (rc0) return rc0;
+  RRAM_REQUIRE(split_k >= 0, "ip_fwd_xbar_bs: negative split_k");
+  if (M == 0 || N == 0) return RRAM_OK;
+  RRAM_REQUIRE(x && w && y, "ip_fwd_xbar_bs: NULL");
+  xb::BsPlan P;
+  xb::make_bs_plan(M, N, K, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
+  const int slabs = P.split * P.chunks;
+  RRAM_REQUIRE(slabs == 1 || (ws != nullptr && ws_bytes >= xb::bs_part_bytes(P)),
+               "ip_fwd_xbar_bs: workspace of %zu bytes below the %zu of %d splits x %d plane chunks", ws_bytes,
+               xb::bs_part_bytes(P), P.split, P.chunks);
+  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * slabs < (1ll << 31), "ip_fwd_xbar_bs: grid too large");
+  hipStream_t s = as_stream(st);
+  auto al16 = [&](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && K % 4 == 0; };
+  const bool xv = al16(x), wv = al16(w);
+
+  const xb::Steps dac = xb::steps_of(*cfg);
+  if (!plan_note("xbar:pack_codes<%s>", xv ? "vec" : "scalar")) {
+    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * P.bm * xb::CRB;
+    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
+    RRAM_REQUIRE(pb != nullptr, "ip_fwd_xbar_bs: packed-code buffer allocation failed");
+    P.apack = pb;
+    const int64_t units = (int64_t)P.tiles_m * P.bm * P.ksteps * 4;
+    if (xv)
+      hipLaunchKernelGGL(xb::k_xbar_pack_codes<true>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
+                         P.ksteps, P.bm, units, dac.dac_xs, dac.dac_qmax);
+    else
+      hipLaunchKernelGGL(xb::k_xbar_pack_codes<false>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
+                         P.ksteps, P.bm, units, dac.dac_xs, dac.dac_qmax);
+    const int rc = launch_status("ip_fwd_xbar_bs pack");
+    if (rc) return rc;
+  }
+  P.w = w;
+  P.bias = bias;
+  P.y = y;
+  P.part = slabs > 1 ? static_cast<int32_t*>(ws) : nullptr;
+  P.relu = relu;
+  if (!plan_note("xbar:ip_bs<%s;p%d>/s%d/c%d", wv ? "vec" : "scalar", P.pc, P.split, P.chunks)) {
+    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs));
+    if (wv)
+      xb::launch_bs<true>(P, grid, s);
+    else
+      xb::launch_bs<false>(P, grid, s);
+    const int rc = launch_status("ip_fwd_xbar_bs");
+    if (rc) return rc;
+  }
+  if (slabs == 1 || plan_note("xbar:finish")) return RRAM_OK;
+  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s, P.part, slabs, M, N, 1,
+                     P.step, bias, relu, y);
+  return launch_status("ip_fwd_xbar_bs finish");
+}
+
+int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
+                                   int split_k, size_t ws_bytes, char* out, size_t cap) {
+  rram::PlanScope sc;
+  auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
+  const int rc = rram_ip_fwd_xbar_bs(ptr(x_align16), ptr(w_align16), nullptr, ptr(1), M, N, K, 0, cfg, 0, split_k,
+                                     ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

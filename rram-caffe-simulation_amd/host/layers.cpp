@@ -137,12 +137,14 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
   }
 }
 
-// crossbar_param { rows adc_bits adc_range [dac_bits dac_range] }, or the Net
-// options `crossbar` (InnerProduct) / `crossbar_conv` (Convolution)
-// ("rows,adc_bits,adc_range[,dac_bits,dac_range]", handed down as
+// crossbar_param { rows adc_bits adc_range [dac_bits dac_range [bit_serial]] },
+// or the Net options `crossbar` (InnerProduct) / `crossbar_conv` (Convolution)
+// ("rows,adc_bits,adc_range[,dac_bits,dac_range[,bit_serial]]", handed down as
 // rram_crossbar to layers without the message).  False: neither is set.
-static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c) {
+// *bit_serial: the bit-serial read-out (rram_ip_fwd_xbar_bs) is asked for.
+static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c, bool* bit_serial) {
   const Msg* xp = lp.sub("crossbar_param");
+  *bit_serial = false;
   if (xp == nullptr && !lp.has("rram_crossbar")) return false;
   *c = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
   if (xp != nullptr) {
@@ -151,6 +153,7 @@ static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg*
     c->adc_range = static_cast<float>(xp->num("adc_range", 0.0));
     c->dac_bits = static_cast<int32_t>(xp->integer("dac_bits", 0));
     c->dac_range = static_cast<float>(xp->num("dac_range", 1.0));
+    *bit_serial = xp->boolean("bit_serial", false);
     return true;
   }
   std::vector<double> v;
@@ -161,12 +164,13 @@ static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg*
   } catch (const std::exception&) {
     v.clear();
   }
-  CAFFE_CHECK(v.size() == 3 || v.size() == 5, name << ": option crossbar wants "
-                                                   << "rows,adc_bits,adc_range[,dac_bits,dac_range]");
+  CAFFE_CHECK(v.size() == 3 || v.size() == 5 || v.size() == 6,
+              name << ": option crossbar wants rows,adc_bits,adc_range[,dac_bits,dac_range[,bit_serial]]");
   c->rows = static_cast<int32_t>(v[0]);
   c->adc_bits = static_cast<int32_t>(v[1]);
   c->adc_range = static_cast<float>(v[2]);
-  if (v.size() == 5) c->dac_bits = static_cast<int32_t>(v[3]), c->dac_range = static_cast<float>(v[4]);
+  if (v.size() >= 5) c->dac_bits = static_cast<int32_t>(v[3]), c->dac_range = static_cast<float>(v[4]);
+  *bit_serial = v.size() == 6 && v[5] != 0.0;
   return true;
 }
 
@@ -188,7 +192,9 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom
   CAFFE_CHECK(desc_.channels % desc_.group == 0 && desc_.num_output % desc_.group == 0,
               "Convolution: channels/num_output must be divisible by group");
   bias_term_ = cp.boolean("bias_term", true);
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_);
+  bool bit_serial = false;
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial);
+  CAFFE_CHECK(!bit_serial, this->name() << ": bit_serial is not served for Convolution");
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan
     // query for one image (before any blob is allocated: no device is touched)
@@ -431,13 +437,17 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
     FillBlob(this->blobs_[1].get(), ip.sub_or_empty("bias_filler"), seed, 1);
   }
   this->param_propagate_down_.assign(this->blobs_.size(), true);
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_);
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_);
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan query
+    // (the bit-serial one with the workspace its plane chunks need)
     CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
     char id[8];
-    CAFFE_CHECK(rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id) > 0,
-                this->name() << ": crossbar_param: " << rram_last_error());
+    const int rc = xbar_bs_ ? rram_ip_fwd_xbar_bs_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0,
+                                                             rram_ip_fwd_xbar_bs_workspace(1, N_, K_, &xbar_, 0), id,
+                                                             sizeof id)
+                            : rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id);
+    CAFFE_CHECK(rc > 0, this->name() << ": crossbar_param: " << rram_last_error());
   }
 }
 
@@ -475,10 +485,11 @@ void InnerProductLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bott
     const Dtype* b = !bias_term_ ? nullptr : group_param_[1] ? group_param_[1] : this->blobs_[1]->gpu_data();
     const Dtype* x = bottom[0]->gpu_data();
     Dtype* y = top[0]->mutable_gpu_data();
+    const auto fwd = xbar_bs_ ? rram_ip_fwd_xbar_bs : rram_ip_fwd_xbar;
     for (int g = 0; g < groups_; ++g)
-      RRAM_CALL(rram_ip_fwd_xbar(x + (int64_t)g * Mg * K_, w + g * group_stride_[0], b ? b + g * group_stride_[1] : b,
-                                 y + (int64_t)g * Mg * N_, Mg, N_, K_, 0, &xbar_, fused_relu ? 1 : 0, 0, ws,
-                                 Caffe::workspace_size(), Caffe::stream()));
+      RRAM_CALL(fwd(x + (int64_t)g * Mg * K_, w + g * group_stride_[0], b ? b + g * group_stride_[1] : b,
+                    y + (int64_t)g * Mg * N_, Mg, N_, K_, 0, &xbar_, fused_relu ? 1 : 0, 0, ws, Caffe::workspace_size(),
+                    Caffe::stream()));
     return;
   }
   if (groups_ > 1) {  // map groups: no packed-row shortcut (rram_ip_fwd_groups has no rows form)

@@ -120,11 +120,13 @@ class InnerProductLayer : public Layer<Dtype> {
   size_t ws_request() const {
     const size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
     if (!xbar_on_) return f32;
-    return std::max(f32, rram_ip_fwd_xbar_workspace(M_ / groups_, N_, K_, &xbar_, 0));
+    const auto need = xbar_bs_ ? rram_ip_fwd_xbar_bs_workspace : rram_ip_fwd_xbar_workspace;
+    return std::max(f32, need(M_ / groups_, N_, K_, &xbar_, 0));
   }
   // crossbar_param (or the Net option `crossbar`): the forward is the
-  // crossbar-tiled ADC read-out (rram_ip_fwd_xbar), the backward unchanged
-  bool xbar_on_ = false;
+  // crossbar-tiled ADC read-out (rram_ip_fwd_xbar; with bit_serial set
+  // rram_ip_fwd_xbar_bs, one conversion per input bit plane), the backward unchanged
+  bool xbar_on_ = false, xbar_bs_ = false;
   rram_xbar_cfg xbar_{};
   uint64_t in_rows_key_ = 0;  // the packed-row companion this layer reads (Reshape; 0: none)
   // set_map_groups: the batch rows are groups_ groups of M_ / groups_ rows,

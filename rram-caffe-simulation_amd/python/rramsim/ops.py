@@ -460,6 +460,23 @@ def ip_fwd_xbar_kernel_ids(M, N, K_, cfg, x_align16=True, w_align16=True, split_
                      split_k, int(ws_bytes))
 
 
+def ip_fwd_xbar_bs(x, w, bias, y, M, N, K_, cfg, transpose=False, relu=False, split_k=0, workspace=None):
+    """rram_ip_fwd_xbar_bs: the bit-serial read-out, one ADC conversion per input bit plane and crossbar tile
+    (cfg.dac_bits > 0; cfg.adc_range is one plane's full scale; split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_fwd_xbar_bs(_p(x), _p(w), _p(bias), _p(y), M, N, K_, int(transpose), C.byref(cfg),
+                                       int(relu), split_k, _p(workspace), wsb, _stream()), "ip_fwd_xbar_bs")
+
+
+def ip_fwd_xbar_bs_workspace(M, N, K_, cfg, split_k=0):
+    return _lib().rram_ip_fwd_xbar_bs_workspace(M, N, K_, C.byref(cfg), split_k)
+
+
+def ip_fwd_xbar_bs_kernel_ids(M, N, K_, cfg, x_align16=True, w_align16=True, split_k=0, ws_bytes=0):
+    return _id_lines(_lib().rram_ip_fwd_xbar_bs_kernel_ids, M, N, K_, C.byref(cfg), int(x_align16), int(w_align16),
+                     split_k, int(ws_bytes))
+
+
 def conv_fwd_xbar(d, x, w, bias, y, cfg, relu=False, split_k=0, workspace=None):
     """rram_conv2d_fwd_xbar: y = the ADC read-out of conv(x, w) from crossbars of cfg.rows rows of the
     unrolled kernel (d: a conv_desc; split_k 0: planner)."""

@@ -2,11 +2,13 @@
 shapes (the same MFMA count without the per-tile rounding): rram_ip_fwd_xbar
 beside rram_ip_fwd on the fc6 / fc7 / CIFAR ip1 shapes, or with --conv
 rram_conv2d_fwd_xbar beside rram_conv2d_fwd on AlexNet conv2 / conv3, VGG11
-conv2 / conv8 and a GoogLeNet 1x1.  Call times from device events (every launch
+conv2 / conv8 and a GoogLeNet 1x1, or with --serial the bit-serial
+rram_ip_fwd_xbar_bs beside rram_ip_fwd_xbar with the same DAC (dac_bits 4 and 8)
+on the InnerProduct shapes.  Call times from device events (every launch
 of the call included), the two alternated in one process, the median and range
 of REPS windows of ITERS calls each.
 
-    python scripts/xbar_bench.py [--conv] [out.txt]
+    python scripts/xbar_bench.py [--conv | --serial] [out.txt]
 """
 import sys
 from pathlib import Path
@@ -73,6 +75,29 @@ def ip_rows():
     return lines
 
 
+def serial_rows():
+    lines = ["shape  M x N x K  R B b | bit-serial us (min..max) ids | parallel xbar us (min..max) ids | ratio | "
+             "MFMA count ratio (b - 1) / 2 | bit-serial share of 416.7 TFLOP/s"]
+    for name, M, N, K, R, B in SHAPES:
+        for b in (4, 8):
+            g = torch.Generator(device="cuda").manual_seed(1)
+            x = torch.randn(M, K, device="cuda", generator=g)
+            w = torch.randn(N, K, device="cuda", generator=g) * K ** -0.5
+            bias = torch.randn(N, device="cuda", generator=g)
+            y = torch.empty(M, N, device="cuda")
+            cfg = ops.xbar_cfg(R, B, 4.0, b, 4.0)
+            wss = torch.empty(max(1, ops.ip_fwd_xbar_bs_workspace(M, N, K, cfg)), dtype=torch.uint8, device="cuda")
+            wsx = torch.empty(max(1, ops.ip_fwd_xbar_workspace(M, N, K, cfg)), dtype=torch.uint8, device="cuda")
+            fs = lambda: ops.ip_fwd_xbar_bs(x, w, bias, y, M, N, K, cfg, relu=True, workspace=wss)  # noqa: E731
+            fx = lambda: ops.ip_fwd_xbar(x, w, bias, y, M, N, K, cfg, relu=True, workspace=wsx)     # noqa: E731
+            line = row(f"{name}  {M} x {N} x {K}  {R} {B} {b}", fs, fx,
+                       ops.ip_fwd_xbar_bs_kernel_ids(M, N, K, cfg, ws_bytes=wss.numel()),
+                       ops.ip_fwd_xbar_kernel_ids(M, N, K, cfg, ws_bytes=wsx.numel()), 2.0 * M * N * K)
+            head, share = line.rsplit(" | ", 1)
+            lines.append(f"{head} | {(b - 1) / 2:.1f} | {share}")
+    return lines
+
+
 def conv_rows():
     lines = ["shape  x -> Cout k/pad/group  R B | xbar us (min..max) ids | plain us (min..max) ids | ratio | "
              "xbar share of 416.7 TFLOP/s"]
@@ -96,8 +121,10 @@ def conv_rows():
 
 def main():
     assert torch.cuda.is_available(), "needs a GPU"
-    args = [a for a in sys.argv[1:] if a != "--conv"]
-    text = "\n".join(conv_rows() if "--conv" in sys.argv[1:] else ip_rows()) + "\n"
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    args = [a for a in sys.argv[1:] if a not in flags]
+    rows = conv_rows if "--conv" in flags else serial_rows if "--serial" in flags else ip_rows
+    text = "\n".join(rows()) + "\n"
     print(text, end="")
     if args:
         Path(args[0]).write_text(text)

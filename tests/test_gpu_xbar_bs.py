@@ -1,0 +1,214 @@
+"""The bit-serial crossbar read-out (rram_ip_fwd_xbar_bs) against a
+float64 loop over crossbar tiles and input bit planes: bit-exact on exact grids,
+equal to the parallel read-out under an ADC that changes nothing, identical
+under every split and chunking, within the near-tie count on Gaussian inputs,
+through the InnerProduct layer, and refused where the header says so."""
+import numpy as np
+import pytest
+
+gpu = pytest.mark.gpu
+
+
+def ref_bs(x, w, bias, R, B, A, b, X, relu=False):
+    """(y float32, S int64, per-element count of near-tie (tile, plane) pairs, clipped anywhere)."""
+    x, w = x.astype(np.float64), w.astype(np.float64)
+    cmax, qmax = 2 ** (b - 1) - 1, 2 ** (B - 1) - 1
+    xs, step = float(np.float32(X)) / cmax, float(np.float32(A)) / qmax
+    c = np.clip(np.rint(x / float(np.float32(xs))), -cmax, cmax).astype(np.int64)
+    S = np.zeros((x.shape[0], w.shape[0]), np.int64)
+    near = np.zeros(S.shape, np.int64)
+    clipped = False
+    for k0 in range(0, x.shape[1], R):
+        ct, wt = c[:, k0:k0 + R], w[:, k0:k0 + R]
+        for j in range(b - 1):
+            u = np.sign(ct) * ((np.abs(ct) >> j) & 1)
+            r = (u @ wt.T) / step
+            margin = 1e-6 * (np.abs(u) @ np.abs(wt).T) / step
+            near += (np.abs(np.abs(r) % 1.0 - 0.5) <= margin) & (np.abs(r) < qmax + 1)
+            clipped |= bool((np.abs(np.rint(r)) > qmax).any())
+            S += np.clip(np.rint(r), -qmax, qmax).astype(np.int64) << j
+    y = S * float(np.float32(step * xs)) + (0.0 if bias is None else bias.astype(np.float64))
+    return (np.maximum(y, 0.0) if relu else y).astype(np.float32), S, near, clipped
+
+
+def grid(shape, seed, lo=-7, hi=7, scale=2.0 ** -3):
+    return (np.random.default_rng(seed).integers(lo, hi + 1, shape) * scale).astype(np.float32)
+
+
+def cfg_of(R, B, e, b, ex):
+    """(rows, adc_bits, adc_range, dac_bits, dac_range) with step = 2^e and xs = 2^ex."""
+    return (R, B, (2 ** (B - 1) - 1) * 2.0 ** e, b, (2 ** (b - 1) - 1) * 2.0 ** ex)
+
+
+def half_codes(shape, seed, b, ex):
+    """x on half-code points i xs / 2, i in [-2 cmax - 4, 2 cmax + 4]: DAC ties and the clamp both occur."""
+    n = 2 * (2 ** (b - 1) - 1) + 4
+    return grid(shape, seed, -n, n, 2.0 ** (ex - 1))
+
+
+def run(fn, x, w, bias, cfg_args, relu=False, split_k=0, unaligned=False):
+    """fn = "ip_fwd_xbar_bs" or "ip_fwd_xbar" on device copies (unaligned: views one float past an allocation)."""
+    import torch
+    from rramsim import ops
+    M, K = x.shape
+    N = w.shape[0]
+    cfg = ops.xbar_cfg(*cfg_args)
+
+    def dev(a):
+        t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
+        v = t[1:] if unaligned else t[:-1]
+        v.copy_(torch.from_numpy(a.reshape(-1)))
+        return v.view(*a.shape)
+
+    y = torch.full((M, N), float("nan"), device="cuda")
+    ws = torch.empty(max(1, getattr(ops, fn + "_workspace")(M, N, K, cfg, split_k)), dtype=torch.uint8, device="cuda")
+    getattr(ops, fn)(dev(x), dev(w), None if bias is None else dev(bias), y, M, N, K, cfg, relu=relu,
+                     split_k=split_k, workspace=ws)
+    torch.cuda.synchronize()
+    return y.cpu().numpy()
+
+
+def same_bits(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+MID, BIG = (33, 130, 96, 32), (40, 300, 2068, 64)
+# (M, N, K, R), adc_bits, log2(step), dac_bits, bias + relu, unaligned
+EXACT = [((1, 1, 1, 32), 8, -3, 2, False, False),       # one plane
+         (MID, 8, -2, 8, True, False),                  # ragged M and N, one chunk of 7 planes
+         (MID, 4, -2, 4, True, False),                  # the ADC clips
+         ((5, 10, 50, 32), 8, -2, 3, False, True),      # short last tile, scalar loads
+         ((70, 200, 300, 128), 12, -3, 5, False, False),
+         (BIG, 8, -2, 12, True, False)]                 # 33 tiles, two plane chunks, the finish kernel
+
+
+@gpu
+@pytest.mark.parametrize("shape,B,e,b,full,unaligned", EXACT)
+def test_exact_grid_bit_exact(device, shape, B, e, b, full, unaligned):
+    M, N, K, R = shape
+    x, w, bias = half_codes((M, K), 1, b, -4), grid((N, K), 2), (grid((N,), 3) if full else None)
+    cfg = cfg_of(R, B, e, b, -4)
+    ref, S, _, clipped = ref_bs(x, w, bias, R, B, cfg[2], b, cfg[4], full)
+    assert clipped == (B == 4) and np.abs(S).max() < 2 ** 24
+    got = run("ip_fwd_xbar_bs", x, w, bias, cfg, full, unaligned=unaligned)
+    assert same_bits(got, ref), np.abs(got - ref).max()
+
+
+@gpu
+def test_equals_parallel_readout_under_a_fine_adc(device):
+    M, N, K, R = MID
+    x, w, bias = half_codes((M, K), 1, 8, -4), grid((N, K), 2), grid((N,), 3)
+    for B, same in ((16, True), (4, False)):
+        bs = cfg_of(R, B, -3, 8, -4)
+        par = cfg_of(R, B, -3 - 4, 8, -4)               # step' = step * xs
+        a, p = run("ip_fwd_xbar_bs", x, w, bias, bs), run("ip_fwd_xbar", x, w, bias, par)
+        assert same_bits(a, p) == same, B                # 4 bits: the per-plane ADC is in the path
+
+
+@gpu
+def test_split_and_chunk_independence(device):
+    from rramsim import ops
+    M, N, K, R = BIG
+    x, w, bias = half_codes((M, K), 4, 12, -4), grid((N, K), 5), grid((N,), 6)
+    cfg = cfg_of(R, 8, -2, 12, -4)
+    ref = ref_bs(x, w, bias, R, 8, cfg[2], 12, cfg[4])[0]
+    for split in (1, 2, 5, 33, 64):
+        assert same_bits(run("ip_fwd_xbar_bs", x, w, bias, cfg, split_k=split), ref), split
+        ids = ops.ip_fwd_xbar_bs_kernel_ids(M, N, K, ops.xbar_cfg(*cfg), split_k=split, ws_bytes=1 << 30)
+        assert ids == ["xbar:pack_codes<vec>", "xbar:ip_bs<vec;p7>/s%d/c2" % min(split, 33), "xbar:finish"], ids
+
+
+@gpu
+@pytest.mark.parametrize("shape,B,e,b", [((64, 96, 1024, 64), 10, -2, 8), ((17, 40, 2304, 128), 8, 0, 6)])
+def test_gaussian_boundary_aware(device, shape, B, e, b):
+    M, N, K, R = shape
+    g = np.random.default_rng(11)
+    x, w = g.standard_normal((M, K)).astype(np.float32), g.standard_normal((N, K)).astype(np.float32)
+    cfg = cfg_of(R, B, e, b, -5)
+    _, S, near, clipped = ref_bs(x, w, None, R, B, cfg[2], b, cfg[4])
+    assert (near > 0).mean() <= 0.05 and not clipped     # a condition on the inputs, from the reference alone
+    Sg = run("ip_fwd_xbar_bs", x, w, None, cfg).astype(np.float64) / 2.0 ** (e - 5)
+    assert np.array_equal(Sg, np.rint(Sg))
+    print("max |S_gpu - S_ref|", np.abs(Sg - S).max(), "near share", (near > 0).mean())
+    assert (np.abs(Sg - S) <= 2 ** (b - 2) * near).all()  # a tie on the highest plane moves S by 2^(b-2); none: equal
+
+
+NET = ('force_backward: true\n'
+       'layer {{ name: "x" type: "Input" top: "x" input_param {{ shape {{ dim: 37 dim: 100 }} }} }}\n'
+       'layer {{ name: "ip" type: "InnerProduct" bottom: "x" top: "y" {xbar} inner_product_param {{ num_output: 45 '
+       'weight_filler {{ type: "uniform" }} bias_filler {{ type: "uniform" }} }} }}\n'
+       'layer {{ name: "relu" type: "ReLU" bottom: "y" top: "y" }}\n')
+CONV = ('layer {{ name: "x" type: "Input" top: "x" input_param {{ shape {{ dim: 4 dim: 5 dim: 6 dim: 6 }} }} }}\n'
+        'layer {{ name: "conv" type: "Convolution" bottom: "x" top: "y" {xbar} convolution_param {{ num_output: 9 '
+        'kernel_size: 3 pad: 1 }} }}\n')
+
+
+def _net(xbar, options, x, w, b, dy):
+    """(y, dx, dw, db) of the three-layer net on the given blobs."""
+    import torch
+    from rramsim import caffe
+    caffe.set_stream_from_torch()
+    net = caffe.Net(NET.format(xbar=xbar), "train", options)
+    ps = net.params()
+    for t, a in ((net.blob("x"), x), (ps[0]["data"], w), (ps[1]["data"], b)):
+        t.copy_(torch.from_numpy(a).reshape(t.shape))
+    net.clear_param_diffs()
+    net.forward()
+    y = net.blob("y").cpu().numpy()
+    net.blob("y", diff=True).copy_(torch.from_numpy(dy))
+    net.backward()
+    out = (y, net.blob("x", diff=True).cpu().numpy(), ps[0]["diff"].cpu().numpy(), ps[1]["diff"].cpu().numpy())
+    net.close()
+    return out
+
+
+@gpu
+def test_layer_forward_option_backward(device):
+    x, w, b, dy = grid((37, 100), 7), grid((45, 100), 8), grid((45,), 9), grid((37, 45), 10)
+    cfg = (32, 8, 31.75, 4, 0.875)
+    msg = "crossbar_param { rows: 32 adc_bits: 8 adc_range: 31.75 dac_bits: 4 dac_range: 0.875 %s}"
+    y = _net(msg % "bit_serial: true ", None, x, w, b, dy)[0]
+    assert same_bits(y, run("ip_fwd_xbar_bs", x, w, b, cfg, relu=True))
+    assert same_bits(y, _net("", {"crossbar": "32,8,31.75,4,0.875,1"}, x, w, b, dy)[0])
+    par = _net(msg % "", None, x, w, b, dy)[0]
+    assert same_bits(par, run("ip_fwd_xbar", x, w, b, cfg, relu=True)) and not same_bits(par, y)
+    # step 2^-3 with 12 bits and xs 2^-3 change nothing here: the plain net's y, so the plain net's diffs
+    fine = _net("crossbar_param { rows: 32 adc_bits: 12 adc_range: %r dac_bits: 4 dac_range: 0.875 bit_serial: true }"
+                % (2047 * 2.0 ** -3), None, x, w, b, dy)
+    for a, p in zip(fine, _net("", None, x, w, b, dy)):
+        assert same_bits(a, p) and np.abs(a).max() > 0
+
+
+def test_refusals_host_only():
+    """No device is touched: the checks and the plan query are host code."""
+    import ctypes as C
+    from rramsim import _kernels as K, caffe, ops
+    lib = K.load()
+    p = C.c_void_p(1 << 20)
+
+    def call(cfg, Kdim=256, transpose=0, split_k=0, ws_bytes=0):
+        return lib.rram_ip_fwd_xbar_bs(p, p, None, p, 8, 16, Kdim, transpose, C.byref(ops.xbar_cfg(*cfg)), 0, split_k,
+                                       p if ws_bytes else None, ws_bytes, None)
+
+    ok = (64, 8, 4.0, 4, 1.0)
+    bad = [(64, 8, 4.0), (48,) + ok[1:], (0,) + ok[1:], (2048,) + ok[1:], (64, 1, 4.0, 4, 1.0), (64, 17, 4.0, 4, 1.0),
+           (64, 8, 0.0, 4, 1.0), (64, 8, float("nan"), 4, 1.0), (64, 8, 4.0, 1, 1.0), (64, 8, 4.0, 4, 0.0),
+           (64, 8, 4.0, 17, 1.0)]
+    for cfg in bad:
+        assert call(cfg) == K.RRAM_EINVAL, cfg
+    assert call(ok, transpose=1) == K.RRAM_EINVAL
+    assert call((32, 16, 4.0, 16, 1.0), Kdim=96) == K.RRAM_EINVAL       # 3 * 32767^2 >= 2^31
+    wide = ops.xbar_cfg(64, 8, 4.0, 12, 1.0)                            # 11 planes: two chunks
+    assert ops.ip_fwd_xbar_bs_workspace(8, 16, 256, ops.xbar_cfg(*ok), 1) == 0
+    need = ops.ip_fwd_xbar_bs_workspace(8, 16, 256, wide, 4)
+    assert need == 4 * 2 * 8 * 16 * 4
+    assert call((64, 8, 4.0, 12, 1.0), split_k=4, ws_bytes=need - 1) == K.RRAM_EINVAL
+    assert ops.ip_fwd_xbar_bs_kernel_ids(8, 16, 256, ops.xbar_cfg(*ok)) == \
+        ["xbar:pack_codes<vec>", "xbar:ip_bs<vec;p4>/s1/c1"]
+    assert ops.ip_fwd_xbar_bs_kernel_ids(8, 16, 250, wide, split_k=9, ws_bytes=need) == \
+        ["xbar:pack_codes<scalar>", "xbar:ip_bs<scalar;p7>/s4/c2", "xbar:finish"]
+    flag = "crossbar_param { rows: 32 adc_bits: 8 adc_range: 4.0 dac_bits: 4 dac_range: 1.0 bit_serial: true }"
+    with pytest.raises(K.RramError, match="bit_serial is not served for Convolution"):
+        caffe.Net(CONV.format(xbar=flag), "train", None)
+    with pytest.raises(K.RramError, match="bit_serial is not served for Convolution"):
+        caffe.Net(CONV.format(xbar=""), "train", {"crossbar_conv": "32,8,4.0,4,1.0,1"})
