@@ -31,8 +31,11 @@
 // array with the unrolled kernel as its rows: see the comment above the kernel.
 // The bit-serial read-out of the InnerProduct array (k_ip_xbar_bs)
 // converts every input bit plane on its own: see the comment above that kernel.
+// The kernels are built from the shared pieces below; which kernel uses which,
+// and why k_conv_xbar keeps some text of its own, is above k_conv_xbar.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "gemm_common.hpp"
 #include "split3.hpp"
@@ -53,16 +56,17 @@ constexpr int A_LD = (A_U + 255) / 256;
 constexpr int B_B = BN * KS * 4;      // weight bytes per K-step (fp32)
 constexpr int B_LD = BN * (KS / 4) / 256;
 constexpr int STAGE = A_B + B_B;
+// bounds the two stages the source declares; the size the compiler reports for
+// the InnerProduct kernels is larger ("LDS")
 static_assert(2 * STAGE <= 160 * 1024, "LDS");
 
-struct Plan {
-  const char* apack;
+// What every read-out's plan holds: the operands, the K axis in K-steps and
+// crossbar tiles with its split, and the ADC.
+struct Core {
   const float* w;
   const float* bias;
   float* y;
-  int32_t* part;       // int32 slabs [split][M][N] (split > 1)
-  int M, N, K;
-  int tiles_m, tiles_n;
+  int32_t* part;       // int32 slabs [slab][y's layout] (more than one slab)
   int ksteps;          // ceil(K / 32)
   int spt;             // K-steps per crossbar tile (R / 32)
   int ntiles;          // crossbar tiles ceil(K / R)
@@ -70,6 +74,22 @@ struct Plan {
   float step, inv_step, qmax;
   int relu;
 };
+
+struct Plan : Core {
+  const char* apack;
+  int M, N, K;
+  int tiles_m, tiles_n;
+};
+
+// split z's whole crossbar tiles [z tc, (z + 1) tc) as K-steps [s0, s1); the last tile may be short
+struct Span {
+  int s0, s1;
+};
+template <class PlanT>  // Plan, BsPlan (through Core) or ConvPlan
+__device__ __forceinline__ Span tile_span(int z, const PlanT& P) {
+  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
+  return {t0 * P.spt, min(P.ksteps, t1 * P.spt)};
+}
 
 // y of one output: float(S) * step, + bias when there is one, ReLU
 __device__ __forceinline__ float xbar_out(int32_t S, float step, const float* bias, int n, int relu) {
@@ -86,41 +106,182 @@ __device__ __forceinline__ void dac8(float (&v)[8], float xs, float qmax) {
   }
 }
 
+// the ADC code of one partial sum: clamp(rint(p / step), +-qmax), half to even
+__device__ __forceinline__ int32_t adc_code(float p, float inv_step, float qmax) {
+  return static_cast<int32_t>(__builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(p, inv_step)), -qmax, qmax));
+}
+
+// Unit u of a pack kernel, one per (row, K-step, group g, half h): v = the 8
+// activations k = 32 ks + 16 h + 8 g + j of row mrow = tm * bm + row (zero past
+// M and K); returns where that row's row_bytes of K-step ks lie in the slabs
+// [row tile][K-step][bm rows][row_bytes].
+struct PackUnit {
+  int g, h;
+  char* row;
+};
+template <bool VEC>
+__device__ __forceinline__ PackUnit pack_unit(int64_t u, const float* __restrict__ x, int M, int K, int ksteps,
+                                              char* out, int bm, int row_bytes, float (&v)[8]) {
+  const int h = static_cast<int>(u & 1), g = static_cast<int>((u >> 1) & 1);
+  const int64_t r = u >> 2;
+  const int ks = static_cast<int>(r % ksteps);
+  const int64_t mrow = r / ksteps;
+  const int k = ks * KS + 16 * h + 8 * g;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = 0.0f;
+  if (mrow < M) {
+    const float* src = x + mrow * K + k;
+    if (VEC) {  // K % 4 == 0, x 16-byte aligned
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        if (k + 4 * q < K) {
+          const float4 f = *reinterpret_cast<const float4*>(src + 4 * q);
+          v[4 * q] = f.x, v[4 * q + 1] = f.y, v[4 * q + 2] = f.z, v[4 * q + 3] = f.w;
+        }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (k + j < K) v[j] = src[j];
+    }
+  }
+  const int64_t tm = mrow / bm;
+  const int row = static_cast<int>(mrow - tm * bm);
+  return {g, h, out + ((tm * ksteps + ks) * bm + row) * row_bytes};
+}
+
 // x [M][K] fp32 -> DAC -> bf16 terms in the K-step slabs k_ip_xbar copies to
-// LDS (zero past M and K).  One thread per (row, K-step, group, half): 8
-// activations in, 48 bytes out.  dac_qmax = 0: no DAC.
+// LDS (zero past M and K).  One thread per unit: 8 activations in, 48 bytes
+// out.  dac_qmax = 0: no DAC.
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_xbar_pack(const float* __restrict__ x, int M, int K, char* __restrict__ out,
                                                    int ksteps, int64_t units, float dac_xs, float dac_qmax) {
   for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-    const int h = static_cast<int>(u & 1), g = static_cast<int>((u >> 1) & 1);
-    const int64_t r = u >> 2;
-    const int ks = static_cast<int>(r % ksteps);
-    const int64_t mrow = r / ksteps;  // tm * BM + row
-    const int k = ks * KS + 16 * h + 8 * g;
-    float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (mrow < M) {
-      const float* src = x + mrow * K + k;
-      if (VEC) {  // K % 4 == 0, x 16-byte aligned
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          if (k + 4 * q < K) {
-            const float4 f = *reinterpret_cast<const float4*>(src + 4 * q);
-            v[4 * q] = f.x, v[4 * q + 1] = f.y, v[4 * q + 2] = f.z, v[4 * q + 3] = f.w;
-          }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (k + j < K) v[j] = src[j];
-      }
-    }
+    float v[8];
+    const PackUnit U = pack_unit<VEC>(u, x, M, K, ksteps, out, BM, RLB, v);
     dac8(v, dac_xs, dac_qmax);
-    const int64_t tm = mrow / BM;
-    const int row = static_cast<int>(mrow - tm * BM);
-    char* rowp = out + ((tm * ksteps + ks) * BM + row) * RLB;
-    x6::store_terms8(v, rowp + (g * 2 + h) * 48);
-    if (g == 1 && h == 1) *reinterpret_cast<uint4*>(rowp + 192) = make_uint4(0, 0, 0, 0);
+    x6::store_terms8(v, U.row + (U.g * 2 + U.h) * 48);
+    if (U.g == 1 && U.h == 1) *reinterpret_cast<uint4*>(U.row + 192) = make_uint4(0, 0, 0, 0);
   }
+}
+
+// Where quad q (4 k) of weight row `row` lies in a stage's weight region
+// [128 rows][32 fp32], in bytes: the quad index is XOR-swizzled with the row so
+// that the fragment reads are conflict-free.  WStage writes through this and
+// wfrag, right below it, reads: the two must agree.
+__device__ __forceinline__ int wquad_lds(int row, int q) { return row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4); }
+
+// the split fragment of weight row nw for MFMA group g, lane half lh (k = 16 lh
+// + 8 g + j), from a stage's weight region: quads 4 lh + 2 g + u of wquad_lds,
+// addressed in floats (written through wquad_lds itself, k_ip_xbar_bs<vec, PC 7>
+// spills one register more)
+__device__ __forceinline__ x6::Parts wfrag(const char* stage_b, int nw, int lh, int g) {
+  const float* sb = reinterpret_cast<const float*>(stage_b) + nw * KS;
+  float b[8];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
+    b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
+  }
+  x6::Parts p;
+  x6::split8_safe(b, p);
+  return p;
+}
+
+// One K-step of the weights, register-staged: B_LD quads per thread of the 128
+// rows from w0 (row pitch K floats), zero for the rows at and past `rows` and
+// for k past K, stored to the weight region at lds_off of a stage.
+template <bool VEC>
+struct WStage {
+  const float* src[B_LD];  // the quad's first element at K-step 0; nullptr: a row past the matrix
+  int k4[B_LD], lds[B_LD];
+  int K;
+  float4 r[B_LD];
+  __device__ __forceinline__ WStage(const float* w0, int rows, int K_, int lds_off, int tid) : K(K_) {
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+      const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
+      src[i] = row < rows ? w0 + (int64_t)row * K + 4 * q : nullptr;
+      k4[i] = 4 * q;
+      lds[i] = lds_off + wquad_lds(row, q);
+    }
+  }
+  __device__ __forceinline__ void load(int s) {
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+      const int k = s * KS + k4[i];
+      float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (src[i] != nullptr) {
+        const float* p = src[i] + s * KS;
+        if (VEC) {  // K % 4 == 0, w 16-byte aligned
+          if (k < K) f = *reinterpret_cast<const float4*>(p);
+        } else {
+          if (k < K) f.x = p[0];
+          if (k + 1 < K) f.y = p[1];
+          if (k + 2 < K) f.z = p[2];
+          if (k + 3 < K) f.w = p[3];
+        }
+      }
+      r[i] = f;
+    }
+  }
+  __device__ __forceinline__ void store(char* st) const {
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4*>(st + lds[i]) = r[i];
+  }
+};
+
+// the three 8-term runs (h, m, l) of one (group, half) of a packed 208-byte row
+__device__ __forceinline__ x6::Parts term_parts(const char* p) {
+  return {*reinterpret_cast<const x6::bf16x8*>(p), *reinterpret_cast<const x6::bf16x8*>(p + 16),
+          *reinterpret_cast<const x6::bf16x8*>(p + 32)};
+}
+
+// The two-stage pipeline of the two InnerProduct kernels (k_conv_xbar keeps its
+// own single loop) over K-steps [s0, s1), spt of them per crossbar tile:
+// load(s + 1) is issued before compute(stage of s) and store(other stage) comes
+// after it, one barrier per step; adc() after every tile's last step, the
+// short last tile included.  Two levels, crossbar tiles then their K-steps, so
+// that the ADC sits between loops and the accumulator sets stay in place (with
+// one loop and a counter inside, k_ip_xbar_bs's sets become merges of "cleared"
+// and "kept" and spill: DESIGN §7.6).
+template <class Load, class Compute, class Store, class Adc>
+__device__ __forceinline__ void pipeline(char* smem, int stage_bytes, Span k, int spt, Load load, Compute compute,
+                                         Store store, Adc adc) {
+  load(k.s0);
+  store(smem);
+  __syncthreads();
+  for (int s = k.s0; s < k.s1;) {
+    const int se = min(k.s1, s + spt);
+    for (; s < se; ++s) {
+      const int cur = (s - k.s0) & 1;
+      const bool more = s + 1 < k.s1;
+      if (more) load(s + 1);
+      compute(smem + cur * stage_bytes);
+      if (more) store(smem + (cur ^ 1) * stage_bytes);
+      __syncthreads();
+    }
+    adc();
+  }
+}
+
+// The InnerProduct epilogue of MI_ 32 x 32 blocks: lane (lr, lh) holds column
+// n, rows m0 + 32 i + 8 (r >> 2) + 4 lh + (r & 3).  part: the workgroup's
+// int32 slab, or nullptr to write y.
+template <int MI_>
+__device__ __forceinline__ void ip_store(const int32_t (&S)[MI_][16], const Plan& P, int32_t* part, int m0, int n,
+                                         int lh) {
+  if (n >= P.N) return;
+#pragma unroll
+  for (int i = 0; i < MI_; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + 32 * i + 8 * (r >> 2) + 4 * lh + (r & 3);
+      if (m >= P.M) continue;
+      if (part != nullptr)
+        part[(int64_t)m * P.N + n] = S[i][r];
+      else
+        P.y[(int64_t)m * P.N + n] = xbar_out(S[i][r], P.step, P.bias, n, P.relu);
+    }
 }
 
 template <bool VEC>
@@ -135,53 +296,27 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   const int tn = __builtin_amdgcn_readfirstlane((id / P.tiles_m) % P.tiles_n);
   const int z = __builtin_amdgcn_readfirstlane(id / (P.tiles_m * P.tiles_n));
   const int m0 = tm * BM, n0 = tn * BN;
-  // whole crossbar tiles [t0, t1) = K-steps [s0, s1); the last tile may be short
-  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
-  const int s0 = t0 * P.spt, s1 = min(P.ksteps, t1 * P.spt);
 
   // this thread's pieces of a K-step: A_LD 16-byte units of the packed
-  // activations, B_LD quads (row, 4 k) of the weights
+  // activations, copied as they lie, and the weight stager's quads.  The copy
+  // is written here and in k_ip_xbar_bs, not shared: through a function over
+  // ra, k_ip_xbar_bs<PC 7> measured 0.9 % slower, and with ra inside a stager
+  // object it spills 19 registers or more instead of 16 (DESIGN §7.4 "LDS").
   const char* asrc = P.apack + (int64_t)tm * P.ksteps * A_B + tid * 16;
-  const float* bsrc[B_LD];
-  int bq[B_LD], blds[B_LD];
-#pragma unroll
-  for (int i = 0; i < B_LD; ++i) {
-    const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
-    bsrc[i] = n0 + row < P.N ? P.w + (int64_t)(n0 + row) * P.K + 4 * q : nullptr;
-    bq[i] = 4 * q;
-    blds[i] = A_B + row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4);
-  }
   uint4 ra[A_LD];
-  float4 rb[B_LD];
+  WStage<VEC> ws(P.w + (int64_t)n0 * P.K, P.N - n0, P.K, A_B, tid);
   auto gload = [&](int s) {
     const char* a = asrc + (int64_t)s * A_B;
 #pragma unroll
     for (int i = 0; i < A_LD; ++i)
       if (tid + 256 * i < A_U) ra[i] = *reinterpret_cast<const uint4*>(a + 4096 * i);
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      const int k = s * KS + bq[i];
-      float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (bsrc[i] != nullptr) {
-        const float* p = bsrc[i] + s * KS;
-        if (VEC) {  // K % 4 == 0, w 16-byte aligned
-          if (k < P.K) f = *reinterpret_cast<const float4*>(p);
-        } else {
-          if (k < P.K) f.x = p[0];
-          if (k + 1 < P.K) f.y = p[1];
-          if (k + 2 < P.K) f.z = p[2];
-          if (k + 3 < P.K) f.w = p[3];
-        }
-      }
-      rb[i] = f;
-    }
+    ws.load(s);
   };
   auto lstore = [&](char* st) {
 #pragma unroll
     for (int i = 0; i < A_LD; ++i)
       if (tid + 256 * i < A_U) *reinterpret_cast<uint4*>(st + tid * 16 + 4096 * i) = ra[i];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4*>(st + blds[i]) = rb[i];
+    ws.store(st);
   };
 
   floatx16 acc[MI];   // the current crossbar tile's partial sums
@@ -196,24 +331,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
   const int nw = 32 * wave + lr;  // this lane's weight row (output column) inside the tile
   auto compute = [&](const char* st) {
-    const float* sb = reinterpret_cast<const float*>(st + A_B) + nw * KS;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      float b[8];
+      const x6::Parts bp = wfrag(st + A_B, nw, lh, g);
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
-        b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
-      }
-      x6::Parts bp;
-      x6::split8_safe(b, bp);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const char* p = st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48;
-        const x6::Parts a{*reinterpret_cast<const x6::bf16x8*>(p), *reinterpret_cast<const x6::bf16x8*>(p + 16),
-                          *reinterpret_cast<const x6::bf16x8*>(p + 32)};
-        acc[i] = x6::mfma6(a, bp, acc[i]);
-      }
+      for (int i = 0; i < MI; ++i)
+        acc[i] = x6::mfma6(term_parts(st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48), bp, acc[i]);
     }
   };
   // the ADC at a tile boundary: codes into S, the partial sums cleared
@@ -222,45 +345,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(acc[i][r], P.inv_step)), -P.qmax, P.qmax);
-        S[i][r] += static_cast<int32_t>(q);
+        S[i][r] += adc_code(acc[i][r], P.inv_step, P.qmax);
         acc[i][r] = 0.0f;
       }
   };
+  pipeline(smem, STAGE, tile_span(z, P), P.spt, gload, compute, lstore, adc);
 
-  gload(s0);
-  lstore(smem);
-  __syncthreads();
-  int in_tile = 0;
-  for (int s = s0; s < s1; ++s) {
-    const int cur = (s - s0) & 1;
-    const bool more = s + 1 < s1;
-    if (more) gload(s + 1);
-    compute(smem + cur * STAGE);
-    if (++in_tile == P.spt) {
-      adc();
-      in_tile = 0;
-    }
-    if (more) lstore(smem + (cur ^ 1) * STAGE);
-    __syncthreads();
-  }
-  if (in_tile != 0) adc();  // the short last tile
-
-  // lane (lr, lh) holds column lr, rows 32 i + 8 (r >> 2) + 4 lh + (r & 3)
-  const int n = n0 + nw;
-  if (n >= P.N) return;
-  int32_t* part = P.split > 1 ? P.part + (int64_t)z * P.M * P.N : nullptr;
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * i + 8 * (r >> 2) + 4 * lh + (r & 3);
-      if (m >= P.M) continue;
-      if (part != nullptr)
-        part[(int64_t)m * P.N + n] = S[i][r];
-      else
-        P.y[(int64_t)m * P.N + n] = xbar_out(S[i][r], P.step, P.bias, n, P.relu);
-    }
+  ip_store(S, P, P.split > 1 ? P.part + (int64_t)z * P.M * P.N : nullptr, m0, n0 + nw, lh);
 }
 
 // The bit-serial read-out: the DAC code c of every activation is
@@ -300,7 +391,10 @@ struct Bs {
   static constexpr int STAGE = A_B + B_B;
 };
 
-struct BsPlan : Plan {  // Plan::step is out_scale = step * xs
+// The host plans both InnerProduct read-outs in a BsPlan (make_ip_plan); for
+// the parallel one chunks = 1, bm = 128, planes and pc stay 0 and mean
+// nothing, and only its Plan part reaches k_ip_xbar.
+struct BsPlan : Plan {  // bit-serial: Core::step is out_scale = step * xs
   int planes;           // dac_bits - 1
   int pc, chunks;       // planes per chunk, ceil(planes / pc)
   int bm;               // rows of a workgroup tile
@@ -308,33 +402,14 @@ struct BsPlan : Plan {  // Plan::step is out_scale = step * xs
 
 // x [M][K] fp32 -> 16-bit sign-magnitude DAC codes clamp(rint(x / xs), +-cmax)
 // in the K-step slabs k_ip_xbar_bs copies to LDS (zero past M and K, zero
-// pad).  One thread per (row, K-step, group, half): 8 activations in, 16 bytes out.
+// pad).  One thread per unit: 8 activations in, 16 bytes out.
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_xbar_pack_codes(const float* __restrict__ x, int M, int K,
                                                          char* __restrict__ out, int ksteps, int bm, int64_t units,
                                                          float xs, float cmax) {
   for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-    const int h = static_cast<int>(u & 1), g = static_cast<int>((u >> 1) & 1);
-    const int64_t r = u >> 2;
-    const int ks = static_cast<int>(r % ksteps);
-    const int64_t mrow = r / ksteps;  // tm * bm + row
-    const int k = ks * KS + 16 * h + 8 * g;
-    float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (mrow < M) {
-      const float* src = x + mrow * K + k;
-      if (VEC) {  // K % 4 == 0, x 16-byte aligned
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          if (k + 4 * q < K) {
-            const float4 f = *reinterpret_cast<const float4*>(src + 4 * q);
-            v[4 * q] = f.x, v[4 * q + 1] = f.y, v[4 * q + 2] = f.z, v[4 * q + 3] = f.w;
-          }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (k + j < K) v[j] = src[j];
-      }
-    }
+    float v[8];
+    const PackUnit U = pack_unit<VEC>(u, x, M, K, ksteps, out, bm, CRB, v);
     uint32_t cw[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -346,11 +421,8 @@ __global__ void __launch_bounds__(256) k_xbar_pack_codes(const float* __restrict
       }
       cw[p] = c2[0] | c2[1] << 16;
     }
-    const int64_t tm = mrow / bm;
-    const int row = static_cast<int>(mrow - tm * bm);
-    char* rowp = out + ((tm * ksteps + ks) * bm + row) * CRB;
-    *reinterpret_cast<uint4*>(rowp + (g * 2 + h) * 16) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-    if (g == 1 && h == 1) *reinterpret_cast<uint4*>(rowp + 64) = make_uint4(0, 0, 0, 0);
+    *reinterpret_cast<uint4*>(U.row + (U.g * 2 + U.h) * 16) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+    if (U.g == 1 && U.h == 1) *reinterpret_cast<uint4*>(U.row + 64) = make_uint4(0, 0, 0, 0);
   }
 }
 
@@ -371,52 +443,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   const int j0 = (zc / P.split) * PC;          // the chunk's first plane
   const int np = min(PC, P.planes - j0);       // ... and how many it has
   const int m0 = tm * T::BM, n0 = tn * BN;
-  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
-  const int s0 = t0 * P.spt, s1 = min(P.ksteps, t1 * P.spt);
 
-  // this thread's pieces of a K-step: A_LD 16-byte units of the codes, B_LD
-  // quads (row, 4 k) of the weights
+  // this thread's pieces of a K-step: A_LD 16-byte units of the codes, copied as
+  // they lie (as in k_ip_xbar, and why it is written twice: there), and the
+  // weight stager's quads
   const char* asrc = P.apack + (int64_t)tm * P.ksteps * T::A_B + tid * 16;
-  const float* bsrc[B_LD];
-  int bq[B_LD], blds[B_LD];
-#pragma unroll
-  for (int i = 0; i < B_LD; ++i) {
-    const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
-    bsrc[i] = n0 + row < P.N ? P.w + (int64_t)(n0 + row) * P.K + 4 * q : nullptr;
-    bq[i] = 4 * q;
-    blds[i] = T::A_B + row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4);
-  }
   uint4 ra[T::A_LD];
-  float4 rb[B_LD];
+  WStage<VEC> ws(P.w + (int64_t)n0 * P.K, P.N - n0, P.K, T::A_B, tid);
   auto gload = [&](int s) {
     const char* a = asrc + (int64_t)s * T::A_B;
 #pragma unroll
     for (int i = 0; i < T::A_LD; ++i)
       if (tid + 256 * i < T::A_U) ra[i] = *reinterpret_cast<const uint4*>(a + 4096 * i);
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      const int k = s * KS + bq[i];
-      float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (bsrc[i] != nullptr) {
-        const float* p = bsrc[i] + s * KS;
-        if (VEC) {  // K % 4 == 0, w 16-byte aligned
-          if (k < P.K) f = *reinterpret_cast<const float4*>(p);
-        } else {
-          if (k < P.K) f.x = p[0];
-          if (k + 1 < P.K) f.y = p[1];
-          if (k + 2 < P.K) f.z = p[2];
-          if (k + 3 < P.K) f.w = p[3];
-        }
-      }
-      rb[i] = f;
-    }
+    ws.load(s);
   };
   auto lstore = [&](char* st) {
 #pragma unroll
     for (int i = 0; i < T::A_LD; ++i)
       if (tid + 256 * i < T::A_U) *reinterpret_cast<uint4*>(st + tid * 16 + 4096 * i) = ra[i];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4*>(st + blds[i]) = rb[i];
+    ws.store(st);
   };
 
   // a cleared set comes out of the matrix pipe (0 * 0 + 0, the addend an inline
@@ -438,17 +483,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
   const int nw = 32 * wave + lr;  // this lane's weight row (output column) inside the tile
   auto compute = [&](const char* st) {
-    const float* sb = reinterpret_cast<const float*>(st + T::A_B) + nw * KS;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      float b[8];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
-        b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
-      }
-      x6::Parts wp;
-      x6::split8_safe(b, wp);
+      const x6::Parts wp = wfrag(st + T::A_B, nw, lh, g);
 #pragma unroll
       for (int i = 0; i < MI_; ++i) {
         // 8 codes as 4 packed pairs; plane j of a pair is bit j of each half as the
@@ -477,48 +514,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         // every set of the pass is converted (a plane past np has stayed 0 and adds
         // 0): per-plane branches here make the sets merge values, copied out all at once
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float q =
-              __builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(acc[i][j][r], P.inv_step)), -P.qmax, P.qmax);
-          S[i][r] += static_cast<int32_t>(q) * (1 << (j0 + j));
-        }
+        for (int r = 0; r < 16; ++r) S[i][r] += adc_code(acc[i][j][r], P.inv_step, P.qmax) * (1 << (j0 + j));
         acc[i][j] = zero_set();
       }
   };
+  pipeline(smem, T::STAGE, tile_span(z, P), P.spt, gload, compute, lstore, adc);
 
-  gload(s0);
-  lstore(smem);
-  __syncthreads();
-  // two levels, crossbar tiles then their K-steps (the last tile may be short),
-  // so that the ADC sits between loops and the sets stay in place
-  for (int s = s0; s < s1;) {
-    const int se = min(s1, s + P.spt);
-    for (; s < se; ++s) {
-      const int cur = (s - s0) & 1;
-      const bool more = s + 1 < s1;
-      if (more) gload(s + 1);
-      compute(smem + cur * T::STAGE);
-      if (more) lstore(smem + (cur ^ 1) * T::STAGE);
-      __syncthreads();
-    }
-    adc();
-  }
-
-  // lane (lr, lh) holds column lr, rows 32 i + 8 (r >> 2) + 4 lh + (r & 3)
-  const int n = n0 + nw;
-  if (n >= P.N) return;
-  int32_t* part = P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr;
-#pragma unroll
-  for (int i = 0; i < MI_; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * i + 8 * (r >> 2) + 4 * lh + (r & 3);
-      if (m >= P.M) continue;
-      if (part != nullptr)
-        part[(int64_t)m * P.N + n] = S[i][r];
-      else
-        P.y[(int64_t)m * P.N + n] = xbar_out(S[i][r], P.step, P.bias, n, P.relu);
-    }
+  ip_store(S, P, P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr, m0, n0 + nw, lh);
 }
 
 // The crossbar-tiled Convolution forward.  The array of group g
@@ -553,6 +555,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 // writes the two 48-byte term groups (MFMA group g = 0, 1, lane half h) of
 // k_ip_xbar's 208-byte row.  The weights of the group are the [Cout/group][Kg]
 // matrix k_ip_xbar streams: fp32 from HBM, split after the LDS read.
+//
+// What is shared with k_ip_xbar here: tile_span, wfrag, term_parts, adc_code and
+// wquad_lds.  The weight staging, the accumulator clear / ADC loops and the
+// single-level K loop are this kernel's own text: through WStage the <vec>
+// kernel spills 5 scalar registers instead of 3, and through shared functions
+// over acc / S or the two-level pipeline it compiles to 255 VGPRs + 84 AGPRs or
+// measured up to 1.5 % slower (profiles/xbar_refactor.txt).  As written the
+// kernel's ISA is the same as before the pieces were shared.
+//
+// ConvPlan has Core's members by name, in the order it always had (the order
+// of the kernel's arguments is part of that ISA), so tile_span, plan_core and
+// launch_finish are templates over the plan.
 struct ConvPlan {
   const float* x;
   const float* w;
@@ -587,8 +601,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   const int grp = __builtin_amdgcn_readfirstlane(id % P.groups);
   const int z = __builtin_amdgcn_readfirstlane(id / P.groups);
   const int p0 = tp * BM, c0 = tn * BN;
-  const int t0 = z * P.tc, t1 = min(P.ntiles, t0 + P.tc);
-  const int s0 = t0 * P.spt, s1 = min(P.ksteps, t1 * P.spt);
+  const Span ks = tile_span(z, P);
+  const int s0 = ks.s0, s1 = ks.s1;
 
   // the gather: this thread's position and its corner (oh sh - ph, ow sw - pw)
   const int gp = tid & (BM - 1), gh = tid >> 7;
@@ -602,7 +616,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   const int row_step = P.dh * P.W - P.KW * P.dw;        // offset step from tap (i, kw) to (i + 1, 0)
   const int chan_step = P.HW - P.KH * P.dh * P.W;       // ... from tap (kh, 0) of ci to (0, 0) of ci + 1
 
-  // the weights: B_LD quads (row, 4 k) of the group's [Ng][Kg] matrix
+  // the weights: B_LD quads (row, 4 k) of the group's [Ng][Kg] matrix.  This is
+  // WStage's text (and must agree with wquad_lds), kept here: through WStage
+  // k_conv_xbar<vec> spills 5 scalar registers instead of 3.
   const float* bsrc[B_LD];
   int bq[B_LD], blds[B_LD];
 #pragma unroll
@@ -610,7 +626,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int idx = tid + 256 * i, row = idx >> 3, q = idx & 7;
     bsrc[i] = c0 + row < P.Ng ? P.w + ((int64_t)grp * P.Ng + c0 + row) * P.Kg + 4 * q : nullptr;
     bq[i] = 4 * q;
-    blds[i] = A_B + row * (KS * 4) + ((q ^ ((row >> 1) & 7)) << 4);
+    blds[i] = A_B + wquad_lds(row, q);
   }
   float rx[16];
   float4 rb[B_LD];
@@ -676,24 +692,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
   const int nw = 32 * wave + lr;  // this lane's weight row (output channel) inside the tile
   auto compute = [&](const char* st) {
-    const float* sb = reinterpret_cast<const float*>(st + A_B) + nw * KS;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      float b[8];
+      const x6::Parts wp = wfrag(st + A_B, nw, lh, g);
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float4 q = *reinterpret_cast<const float4*>(sb + (((4 * lh + 2 * g + u) ^ ((nw >> 1) & 7)) << 2));
-        b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
-      }
-      x6::Parts wp;
-      x6::split8_safe(b, wp);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const char* p = st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48;
-        const x6::Parts xp{*reinterpret_cast<const x6::bf16x8*>(p), *reinterpret_cast<const x6::bf16x8*>(p + 16),
-                           *reinterpret_cast<const x6::bf16x8*>(p + 32)};
-        acc[i] = x6::mfma6(wp, xp, acc[i]);  // rows = channels, columns = positions
-      }
+      for (int i = 0; i < MI; ++i)  // rows = channels, columns = positions
+        acc[i] = x6::mfma6(wp, term_parts(st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48), acc[i]);
     }
   };
   auto adc = [&]() {
@@ -701,8 +705,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(__fmul_rn(acc[i][r], P.inv_step)), -P.qmax, P.qmax);
-        S[i][r] += static_cast<int32_t>(q);
+        S[i][r] += adc_code(acc[i][r], P.inv_step, P.qmax);
         acc[i][r] = 0.0f;
       }
   };
@@ -818,26 +821,25 @@ void plan_split(int ntiles, int64_t tiles, size_t slab_bytes, int split_k, size_
   split = (ntiles + tc - 1) / tc;
 }
 
-// split_k = 0: toward 256 workgroups, whole tiles, partials within ws_bytes;
-// else the caller's split clamped to the tile count
-void make_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t ws_bytes, Plan& P) {
-  P = Plan{};
-  P.M = M, P.N = N, P.K = K;
-  P.tiles_m = (M + BM - 1) / BM;
-  P.tiles_n = (N + BN - 1) / BN;
+// The core of a plan over K array rows: `tiles` workgroups per split, each
+// split writing slab_bytes when there is more than one (plan_split), the ADC
+// of the configuration.  The operands are the entry point's to fill.
+template <class PlanT>
+void plan_core(PlanT& P, int K, const rram_xbar_cfg& c, int64_t tiles, size_t slab_bytes, int split_k,
+               size_t ws_bytes) {
   P.ksteps = (K + KS - 1) / KS;
   P.spt = c.rows / KS;
   P.ntiles = (K + c.rows - 1) / c.rows;
-  plan_split(P.ntiles, (int64_t)P.tiles_m * P.tiles_n, (size_t)M * N * sizeof(int32_t), split_k, ws_bytes, P.tc,
-             P.split);
+  plan_split(P.ntiles, tiles, slab_bytes, split_k, ws_bytes, P.tc, P.split);
   const Steps st = steps_of(c);
   P.step = st.step, P.inv_step = st.inv_step, P.qmax = st.qmax;
 }
 
-size_t part_bytes(const Plan& P) { return P.split > 1 ? (size_t)P.split * P.M * P.N * sizeof(int32_t) : 0; }
+// the workspace of `slabs` int32 slabs of `outputs` each: none for one slab, which is y
+size_t part_bytes(int slabs, int64_t outputs) { return slabs > 1 ? (size_t)slabs * outputs * sizeof(int32_t) : 0; }
 
-// The bit-serial read-out's checks (host only) and plan.  The DAC is mandatory,
-// and S (so every partial slab too) must fit int32: |S| <= ntiles * qmax * cmax.
+// The bit-serial read-out's checks (host only).  The DAC is mandatory, and S
+// (so every partial slab too) must fit int32: |S| <= ntiles * qmax * cmax.
 int bs_check(int M, int N, int K, const rram_xbar_cfg* c, int transpose) {
   const int rc = check(M, N, K, c, transpose);
   if (rc) return rc;
@@ -849,39 +851,33 @@ int bs_check(int M, int N, int K, const rram_xbar_cfg* c, int transpose) {
   return RRAM_OK;
 }
 
-// up to 4 planes: <PC 4, MI 2>; else chunks of 7 planes on <PC 7, MI 2> (both
-// 64-row tiles).  The chunk count is folded into the planner's
-// workgroup count and slab size, so a multi-chunk problem asks for fewer K splits.
-void make_bs_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t ws_bytes, BsPlan& P) {
+// The plan of either InnerProduct read-out; the parallel one is a BsPlan of one
+// chunk on 128-row tiles whose Plan part goes to k_ip_xbar.  Bit-serial: up to
+// 4 planes on <PC 4, MI 2>, else chunks of 7 planes on <PC 7, MI 2> (both
+// 64-row tiles).  The chunk count is folded into the planner's workgroup count
+// and slab size, so a multi-chunk problem asks for fewer K splits.
+// split_k = 0: toward 256 workgroups, whole tiles, partials within ws_bytes;
+// else the caller's split clamped to the tile count.
+void make_ip_plan(int M, int N, int K, const rram_xbar_cfg& c, bool serial, int split_k, size_t ws_bytes, BsPlan& P) {
   P = BsPlan{};
   P.M = M, P.N = N, P.K = K;
-  P.planes = c.dac_bits - 1;
-  P.pc = P.planes <= 4 ? 4 : 7;
-  P.chunks = (P.planes + P.pc - 1) / P.pc;
-  P.bm = Bs<2>::BM;
+  P.chunks = 1;
+  P.bm = BM;
+  if (serial) {
+    P.planes = c.dac_bits - 1;
+    P.pc = P.planes <= 4 ? 4 : 7;
+    P.chunks = (P.planes + P.pc - 1) / P.pc;
+    P.bm = Bs<2>::BM;
+  }
   P.tiles_m = (M + P.bm - 1) / P.bm;
   P.tiles_n = (N + BN - 1) / BN;
-  P.ksteps = (K + KS - 1) / KS;
-  P.spt = c.rows / KS;
-  P.ntiles = (K + c.rows - 1) / c.rows;
-  plan_split(P.ntiles, (int64_t)P.tiles_m * P.tiles_n * P.chunks, (size_t)M * N * sizeof(int32_t) * P.chunks, split_k,
-             ws_bytes, P.tc, P.split);
-  const Steps st = steps_of(c);
-  const int qmax = (1 << (c.adc_bits - 1)) - 1, cmax = (1 << (c.dac_bits - 1)) - 1;
-  P.step = static_cast<float>(static_cast<double>(c.adc_range) / qmax * (static_cast<double>(c.dac_range) / cmax));
-  P.inv_step = st.inv_step, P.qmax = st.qmax;
-}
-
-size_t bs_part_bytes(const BsPlan& P) {
-  return P.split * P.chunks > 1 ? (size_t)P.split * P.chunks * P.M * P.N * sizeof(int32_t) : 0;
-}
-
-template <bool VEC>
-void launch_bs(const BsPlan& P, dim3 grid, hipStream_t s) {
-  if (P.pc == 4)
-    hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 4, 2>), grid, dim3(256), 0, s, P);
-  else
-    hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 7, 2>), grid, dim3(256), 0, s, P);
+  plan_core(P, K, c, (int64_t)P.tiles_m * P.tiles_n * P.chunks, (size_t)M * N * sizeof(int32_t) * P.chunks, split_k,
+            ws_bytes);
+  if (serial) {  // out_scale
+    const Steps st = steps_of(c);
+    P.step = static_cast<float>(static_cast<double>(c.adc_range) / st.qmax *
+                                (static_cast<double>(c.dac_range) / st.dac_qmax));
+  }
 }
 
 // The convolution's checks (host only; d gets its output shape) and plan.
@@ -915,17 +911,118 @@ void make_conv_plan(const rram_conv_desc& d, const rram_xbar_cfg& c, int split_k
   P.wo_div = make_fastdiv(static_cast<uint32_t>(d.out_w));
   P.tiles_p = (P.M + BM - 1) / BM;
   P.tiles_c = (P.Ng + BN - 1) / BN;
-  P.ksteps = (P.Kg + KS - 1) / KS;
-  P.spt = c.rows / KS;
-  P.ntiles = (P.Kg + c.rows - 1) / c.rows;
   P.total = (int64_t)d.num * d.num_output * P.HoWo;
-  plan_split(P.ntiles, (int64_t)P.tiles_p * P.tiles_c * P.groups, (size_t)P.total * sizeof(int32_t), split_k, ws_bytes,
-             P.tc, P.split);
+  plan_core(P, P.Kg, c, (int64_t)P.tiles_p * P.tiles_c * P.groups, (size_t)P.total * sizeof(int32_t), split_k,
+            ws_bytes);
   const Steps st = steps_of(c);
-  P.step = st.step, P.inv_step = st.inv_step, P.qmax = st.qmax, P.dac_xs = st.dac_xs, P.dac_qmax = st.dac_qmax;
+  P.dac_xs = st.dac_xs, P.dac_qmax = st.dac_qmax;
 }
 
-size_t conv_part_bytes(const ConvPlan& P) { return P.split > 1 ? (size_t)P.split * P.total * sizeof(int32_t) : 0; }
+// The pieces every entry point ends with or passes through.
+
+// whether an operand with rows of K floats takes the 16-byte loads
+bool al16(const void* p, int K) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && K % 4 == 0; }
+
+// f(std::true_type) or f(std::false_type): a kernel's VEC instantiation chosen at run time
+template <class F>
+void by_vec(bool vec, F f) {
+  if (vec)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+// the caller's workspace must hold the `need` bytes of the plan's slabs; tail: what multiplies the splits
+int require_ws(const char* who, const void* ws, size_t ws_bytes, size_t need, int split, int chunks) {
+  if (need == 0 || (ws != nullptr && ws_bytes >= need)) return RRAM_OK;
+  RRAM_REQUIRE(chunks == 0, "%s: workspace of %zu bytes below the %zu of %d splits x %d plane chunks", who, ws_bytes,
+               need, split, chunks);
+  RRAM_REQUIRE(false, "%s: workspace of %zu bytes below the %zu of %d splits", who, ws_bytes, need, split);
+  return RRAM_OK;
+}
+
+// the slabs summed into y [M][N][inner], unless y was written by the one slab's epilogue
+template <class PlanT>
+int launch_finish(const char* what, const PlanT& P, int slabs, int M, int N, int inner, hipStream_t s) {
+  if (slabs == 1 || plan_note("xbar:finish")) return RRAM_OK;
+  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks((int64_t)M * N * inner)), dim3(256), 0, s, P.part, slabs, M,
+                     N, inner, P.step, P.bias, P.relu, P.y);
+  return launch_status(what);
+}
+
+// an operand for the host-only id queries: never dereferenced, only its alignment is read
+float* fake_ptr(int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); }
+
+size_t ip_workspace(bool serial, int M, int N, int K, const rram_xbar_cfg* cfg, int split_k) {
+  if ((serial ? bs_check(M, N, K, cfg, 0) : check(M, N, K, cfg, 0)) != RRAM_OK || M == 0 || N == 0 || split_k < 0)
+    return 0;
+  BsPlan P;
+  make_ip_plan(M, N, K, *cfg, serial, split_k, ~static_cast<size_t>(0), P);
+  return part_bytes(P.split * P.chunks, (int64_t)M * N);
+}
+
+// rram_ip_fwd_xbar and, with serial, rram_ip_fwd_xbar_bs: the checks, the plan
+// and the pack kernel, the read-out kernel and its id differ, the rest is one
+int ip_fwd(bool serial, const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+           int transpose, const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
+           rram_stream_t st) {
+  const char* who = serial ? "ip_fwd_xbar_bs" : "ip_fwd_xbar";
+  const int rc0 = serial ? bs_check(M, N, K, cfg, transpose) : check(M, N, K, cfg, transpose);
+  if (rc0) return rc0;
+  RRAM_REQUIRE(split_k >= 0, "%s: negative split_k", who);
+  if (M == 0 || N == 0) return RRAM_OK;
+  RRAM_REQUIRE(x && w && y, "%s: NULL", who);
+  BsPlan P;
+  make_ip_plan(M, N, K, *cfg, serial, split_k, ws != nullptr ? ws_bytes : 0, P);
+  const int slabs = P.split * P.chunks;
+  const int rcw = require_ws(who, ws, ws_bytes, part_bytes(slabs, (int64_t)M * N), P.split, serial ? P.chunks : 0);
+  if (rcw) return rcw;
+  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * slabs < (1ll << 31), "%s: grid too large", who);
+  hipStream_t s = as_stream(st);
+  const bool xv = al16(x, K), wv = al16(w, K);
+
+  const Steps dac = steps_of(*cfg);
+  if (!plan_note(serial ? "xbar:pack_codes<%s>" : "xbar:pack<%s>", xv ? "vec" : "scalar")) {
+    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * P.bm * (serial ? CRB : RLB);
+    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
+    RRAM_REQUIRE(pb != nullptr, "%s: packed-%s buffer allocation failed", who, serial ? "code" : "activation");
+    P.apack = pb;
+    const int64_t units = (int64_t)P.tiles_m * P.bm * P.ksteps * 4;
+    const dim3 grid(stream_blocks(units));
+    by_vec(xv, [&](auto V) {
+      if (serial)
+        hipLaunchKernelGGL(k_xbar_pack_codes<decltype(V)::value>, grid, dim3(256), 0, s, x, M, K, pb, P.ksteps, P.bm,
+                           units, dac.dac_xs, dac.dac_qmax);
+      else
+        hipLaunchKernelGGL(k_xbar_pack<decltype(V)::value>, grid, dim3(256), 0, s, x, M, K, pb, P.ksteps, units,
+                           dac.dac_xs, dac.dac_qmax);
+    });
+    const int rc = launch_status(serial ? "ip_fwd_xbar_bs pack" : "ip_fwd_xbar pack");
+    if (rc) return rc;
+  }
+  P.w = w;
+  P.bias = bias;
+  P.y = y;
+  P.part = slabs > 1 ? static_cast<int32_t*>(ws) : nullptr;
+  P.relu = relu;
+  const char* wl = wv ? "vec" : "scalar";
+  if (!(serial ? plan_note("xbar:ip_bs<%s;p%d>/s%d/c%d", wl, P.pc, P.split, P.chunks)
+               : plan_note("xbar:ip<%s>/s%d", wl, P.split))) {
+    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs));
+    by_vec(wv, [&](auto V) {
+      constexpr bool VEC = decltype(V)::value;
+      if (!serial)
+        hipLaunchKernelGGL(k_ip_xbar<VEC>, grid, dim3(256), 0, s, static_cast<const Plan&>(P));
+      else if (P.pc == 4)
+        hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 4, 2>), grid, dim3(256), 0, s, P);
+      else
+        hipLaunchKernelGGL((k_ip_xbar_bs<VEC, 7, 2>), grid, dim3(256), 0, s, P);
+    });
+    const int rc = launch_status(who);
+    if (rc) return rc;
+  }
+  return launch_finish(serial ? "ip_fwd_xbar_bs finish" : "ip_fwd_xbar finish", P, slabs, M, N, 1, s);
+}
 
 }  // namespace xb
 }  // namespace
@@ -934,143 +1031,39 @@ size_t conv_part_bytes(const ConvPlan& P) { return P.split > 1 ? (size_t)P.split
 extern "C" {
 
 size_t rram_ip_fwd_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k) {
-  if (rram::xb::check(M, N, K, cfg, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
-  rram::xb::Plan P;
-  rram::xb::make_plan(M, N, K, *cfg, split_k, ~static_cast<size_t>(0), P);
-  return rram::xb::part_bytes(P);
+  return rram::xb::ip_workspace(false, M, N, K, cfg, split_k);
 }
 
 int rram_ip_fwd_xbar(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int transpose,
                      const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes, rram_stream_t st) {
-  using namespace rram;
-  const int rc0 = xb::check(M, N, K, cfg, transpose);
-  if (rc0) return rc0;
-  RRAM_REQUIRE(split_k >= 0, "ip_fwd_xbar: negative split_k");
-  if (M == 0 || N == 0) return RRAM_OK;
-  RRAM_REQUIRE(x && w && y, "ip_fwd_xbar: NULL");
-  xb::Plan P;
-  xb::make_plan(M, N, K, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
-  RRAM_REQUIRE(P.split == 1 || (ws != nullptr && ws_bytes >= xb::part_bytes(P)),
-               "ip_fwd_xbar: workspace of %zu bytes below the %zu of %d splits", ws_bytes, xb::part_bytes(P), P.split);
-  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * P.split < (1ll << 31), "ip_fwd_xbar: grid too large");
-  hipStream_t s = as_stream(st);
-  auto al16 = [&](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && K % 4 == 0; };
-  const bool xv = al16(x), wv = al16(w);
-
-  const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * xb::A_B;
-  const float dac_xs = xb::steps_of(*cfg).dac_xs, dac_qmax = xb::steps_of(*cfg).dac_qmax;
-  if (!plan_note("xbar:pack<%s>", xv ? "vec" : "scalar")) {
-    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
-    RRAM_REQUIRE(pb != nullptr, "ip_fwd_xbar: packed-activation buffer allocation failed");
-    P.apack = pb;
-    const int64_t units = (int64_t)P.tiles_m * xb::BM * P.ksteps * 4;
-    if (xv)
-      hipLaunchKernelGGL(xb::k_xbar_pack<true>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb, P.ksteps,
-                         units, dac_xs, dac_qmax);
-    else
-      hipLaunchKernelGGL(xb::k_xbar_pack<false>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb, P.ksteps,
-                         units, dac_xs, dac_qmax);
-    const int rc = launch_status("ip_fwd_xbar pack");
-    if (rc) return rc;
-  }
-  P.w = w;
-  P.bias = bias;
-  P.y = y;
-  P.part = P.split > 1 ? static_cast<int32_t*>(ws) : nullptr;
-  P.relu = relu;
-  if (!plan_note("xbar:ip<%s>/s%d", wv ? "vec" : "scalar", P.split)) {
-    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * P.split));
-    if (wv)
-      hipLaunchKernelGGL(xb::k_ip_xbar<true>, grid, dim3(256), 0, s, P);
-    else
-      hipLaunchKernelGGL(xb::k_ip_xbar<false>, grid, dim3(256), 0, s, P);
-    const int rc = launch_status("ip_fwd_xbar");
-    if (rc) return rc;
-  }
-  if (P.split == 1 || plan_note("xbar:finish")) return RRAM_OK;
-  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s, P.part, P.split, M, N,
-                     1, P.step, bias, relu, y);
-  return launch_status("ip_fwd_xbar finish");
+  return rram::xb::ip_fwd(false, x, w, bias, y, M, N, K, transpose, cfg, relu, split_k, ws, ws_bytes, st);
 }
 
 int rram_ip_fwd_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                 int split_k, size_t ws_bytes, char* out, size_t cap) {
+  using rram::xb::fake_ptr;
   rram::PlanScope sc;
-  auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
-  const int rc = rram_ip_fwd_xbar(ptr(x_align16), ptr(w_align16), nullptr, ptr(1), M, N, K, 0, cfg, 0, split_k,
-                                  ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
+  const int rc = rram_ip_fwd_xbar(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg, 0,
+                                  split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 
 size_t rram_ip_fwd_xbar_bs_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k) {
-  if (rram::xb::bs_check(M, N, K, cfg, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
-  rram::xb::BsPlan P;
-  rram::xb::make_bs_plan(M, N, K, *cfg, split_k, ~static_cast<size_t>(0), P);
-  return rram::xb::bs_part_bytes(P);
+  return rram::xb::ip_workspace(true, M, N, K, cfg, split_k);
 }
 
 int rram_ip_fwd_xbar_bs(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
                         int transpose, const rram_xbar_cfg* cfg, int relu, int split_k, void* ws, size_t ws_bytes,
                         rram_stream_t st) {
-  using namespace rram;
-  const int rc0 = xb::bs_check(M, N, K, cfg, transpose);
-  if (rc0) return rc0;
-  RRAM_REQUIRE(split_k >= 0, "ip_fwd_xbar_bs: negative split_k");
-  if (M == 0 || N == 0) return RRAM_OK;
-  RRAM_REQUIRE(x && w && y, "ip_fwd_xbar_bs: NULL");
-  xb::BsPlan P;
-  xb::make_bs_plan(M, N, K, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
-  const int slabs = P.split * P.chunks;
-  RRAM_REQUIRE(slabs == 1 || (ws != nullptr && ws_bytes >= xb::bs_part_bytes(P)),
-               "ip_fwd_xbar_bs: workspace of %zu bytes below the %zu of %d splits x %d plane chunks", ws_bytes,
-               xb::bs_part_bytes(P), P.split, P.chunks);
-  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * slabs < (1ll << 31), "ip_fwd_xbar_bs: grid too large");
-  hipStream_t s = as_stream(st);
-  auto al16 = [&](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && K % 4 == 0; };
-  const bool xv = al16(x), wv = al16(w);
-
-  const xb::Steps dac = xb::steps_of(*cfg);
-  if (!plan_note("xbar:pack_codes<%s>", xv ? "vec" : "scalar")) {
-    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * P.bm * xb::CRB;
-    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
-    RRAM_REQUIRE(pb != nullptr, "ip_fwd_xbar_bs: packed-code buffer allocation failed");
-    P.apack = pb;
-    const int64_t units = (int64_t)P.tiles_m * P.bm * P.ksteps * 4;
-    if (xv)
-      hipLaunchKernelGGL(xb::k_xbar_pack_codes<true>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
-                         P.ksteps, P.bm, units, dac.dac_xs, dac.dac_qmax);
-    else
-      hipLaunchKernelGGL(xb::k_xbar_pack_codes<false>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
-                         P.ksteps, P.bm, units, dac.dac_xs, dac.dac_qmax);
-    const int rc = launch_status("ip_fwd_xbar_bs pack");
-    if (rc) return rc;
-  }
-  P.w = w;
-  P.bias = bias;
-  P.y = y;
-  P.part = slabs > 1 ? static_cast<int32_t*>(ws) : nullptr;
-  P.relu = relu;
-  if (!plan_note("xbar:ip_bs<%s;p%d>/s%d/c%d", wv ? "vec" : "scalar", P.pc, P.split, P.chunks)) {
-    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs));
-    if (wv)
-      xb::launch_bs<true>(P, grid, s);
-    else
-      xb::launch_bs<false>(P, grid, s);
-    const int rc = launch_status("ip_fwd_xbar_bs");
-    if (rc) return rc;
-  }
-  if (slabs == 1 || plan_note("xbar:finish")) return RRAM_OK;
-  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks((int64_t)M * N)), dim3(256), 0, s, P.part, slabs, M, N, 1,
-                     P.step, bias, relu, y);
-  return launch_status("ip_fwd_xbar_bs finish");
+  return rram::xb::ip_fwd(true, x, w, bias, y, M, N, K, transpose, cfg, relu, split_k, ws, ws_bytes, st);
 }
 
 int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                    int split_k, size_t ws_bytes, char* out, size_t cap) {
+  using rram::xb::fake_ptr;
   rram::PlanScope sc;
-  auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
-  const int rc = rram_ip_fwd_xbar_bs(ptr(x_align16), ptr(w_align16), nullptr, ptr(1), M, N, K, 0, cfg, 0, split_k,
-                                     ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
+  const int rc = rram_ip_fwd_xbar_bs(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
+                                     0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 
@@ -1080,7 +1073,7 @@ size_t rram_conv2d_fwd_xbar_workspace(const rram_conv_desc* d_in, const rram_xba
   if (rram::xb::conv_check(d, cfg, split_k) != RRAM_OK || d.num == 0) return 0;
   rram::xb::ConvPlan P;
   rram::xb::make_conv_plan(d, *cfg, split_k, ~static_cast<size_t>(0), P);
-  return rram::xb::conv_part_bytes(P);
+  return rram::xb::part_bytes(P.split, P.total);
 }
 
 int rram_conv2d_fwd_xbar(const rram_conv_desc* d_in, const float* x, const float* w, const float* bias, float* y,
@@ -1095,37 +1088,32 @@ int rram_conv2d_fwd_xbar(const rram_conv_desc* d_in, const float* x, const float
   RRAM_REQUIRE(x && w && y, "conv2d_fwd_xbar: NULL pointer");
   xb::ConvPlan P;
   xb::make_conv_plan(d, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
-  RRAM_REQUIRE(P.split == 1 || (ws != nullptr && ws_bytes >= xb::conv_part_bytes(P)),
-               "conv2d_fwd_xbar: workspace of %zu bytes below the %zu of %d splits", ws_bytes, xb::conv_part_bytes(P),
-               P.split);
+  const int rcw = xb::require_ws("conv2d_fwd_xbar", ws, ws_bytes, xb::part_bytes(P.split, P.total), P.split, 0);
+  if (rcw) return rcw;
   const int64_t wgs = (int64_t)P.tiles_p * P.tiles_c * P.groups * P.split;
   RRAM_REQUIRE(wgs < (1ll << 31) && (int64_t)P.tiles_p * xb::BM < (1ll << 31), "conv2d_fwd_xbar: grid too large");
   hipStream_t s = as_stream(st);
-  const bool wv = (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && P.Kg % 4 == 0;
+  const bool wv = xb::al16(w, P.Kg);
   P.x = x, P.w = w, P.bias = bias, P.y = y;
   P.part = P.split > 1 ? static_cast<int32_t*>(ws) : nullptr;
   P.relu = relu;
   if (!plan_note("xbar:conv<%s>/s%d", wv ? "vec" : "scalar", P.split)) {
     const dim3 grid(static_cast<unsigned>(wgs));
-    if (wv)
-      hipLaunchKernelGGL(xb::k_conv_xbar<true>, grid, dim3(256), 0, s, P);
-    else
-      hipLaunchKernelGGL(xb::k_conv_xbar<false>, grid, dim3(256), 0, s, P);
+    xb::by_vec(wv, [&](auto V) {
+      hipLaunchKernelGGL(xb::k_conv_xbar<decltype(V)::value>, grid, dim3(256), 0, s, P);
+    });
     const int rc = launch_status("conv2d_fwd_xbar");
     if (rc) return rc;
   }
-  if (P.split == 1 || plan_note("xbar:finish")) return RRAM_OK;
-  hipLaunchKernelGGL(xb::k_xbar_finish, dim3(stream_blocks(P.total)), dim3(256), 0, s, P.part, P.split, d.num,
-                     d.num_output, P.HoWo, P.step, bias, relu, y);
-  return launch_status("conv2d_fwd_xbar finish");
+  return xb::launch_finish("conv2d_fwd_xbar finish", P, P.split, d.num, d.num_output, P.HoWo, s);
 }
 
 int rram_conv2d_fwd_xbar_kernel_ids(const rram_conv_desc* d, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                     int split_k, size_t ws_bytes, char* out, size_t cap) {
+  using rram::xb::fake_ptr;
   rram::PlanScope sc;
-  auto ptr = [](int align16) { return reinterpret_cast<float*>(uintptr_t{1} << 20 | (align16 ? 0u : 4u)); };
-  const int rc = rram_conv2d_fwd_xbar(d, ptr(x_align16), ptr(w_align16), nullptr, ptr(1), cfg, 0, split_k,
-                                      ws_bytes ? ptr(1) : nullptr, ws_bytes, nullptr);
+  const int rc = rram_conv2d_fwd_xbar(d, fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), cfg, 0,
+                                      split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

@@ -5,6 +5,7 @@ near-tie tiles on Gaussian inputs; identical bits under every split over K;
 and through the InnerProduct layer, the Net option and the Monte-Carlo driver."""
 import numpy as np
 import pytest
+from _xbar_cases import IP_NET, adc_tile, dac_codes, grid, run_ip, run_net
 
 gpu = pytest.mark.gpu
 
@@ -14,48 +15,21 @@ def ref_xbar(x, w, bias, R, bits, rng, relu=False, dac=None):
     x, w = x.astype(np.float64), w.astype(np.float64)
     if dac:
         q = 2 ** (dac[0] - 1) - 1
-        x = np.clip(np.rint(x / (dac[1] / q)), -q, q) * (dac[1] / q)
+        x = dac_codes(x, dac[1] / q, q) * (dac[1] / q)
     qmax = 2 ** (bits - 1) - 1
     step = float(np.float32(rng)) / qmax
     S = np.zeros((x.shape[0], w.shape[0]), np.int64)
     near = np.zeros(S.shape, np.int64)
     clipped = False
     for k0 in range(0, x.shape[1], R):
-        xt, wt = x[:, k0:k0 + R], w[:, k0:k0 + R]
-        r = (xt @ wt.T) / step
-        margin = 1e-6 * (np.abs(xt) @ np.abs(wt).T) / step
-        near += (np.abs(np.abs(r) % 1.0 - 0.5) <= margin) & (np.abs(r) < qmax + 1)
-        clipped |= bool((np.abs(np.rint(r)) > qmax).any())
-        S += np.clip(np.rint(r), -qmax, qmax).astype(np.int64)
+        q, n, c = adc_tile(x[:, k0:k0 + R], w[:, k0:k0 + R], step, qmax)
+        S, near, clipped = S + q, near + n, clipped | c
     y = S * step + (0.0 if bias is None else bias.astype(np.float64))
     return (np.maximum(y, 0.0) if relu else y).astype(np.float32), S, near, clipped
 
 
-def grid(shape, seed, lo=-7, hi=7, scale=2.0 ** -3):
-    return (np.random.default_rng(seed).integers(lo, hi + 1, shape) * scale).astype(np.float32)
-
-
-def dev(a, unaligned=False):
-    """a on the GPU; unaligned: as a view one float past an aligned allocation."""
-    import torch
-    t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
-    v = t[1:] if unaligned else t[:-1]
-    v.copy_(torch.from_numpy(a.reshape(-1)))
-    return v.view(*a.shape)
-
-
 def run_xbar(x, w, bias, cfg_args, relu=False, split_k=0, unaligned=False):
-    import torch
-    from rramsim import ops
-    M, K = x.shape
-    N = w.shape[0]
-    cfg = ops.xbar_cfg(*cfg_args)
-    y = torch.full((M, N), float("nan"), device="cuda")
-    ws = torch.empty(max(1, ops.ip_fwd_xbar_workspace(M, N, K, cfg, split_k)), dtype=torch.uint8, device="cuda")
-    ops.ip_fwd_xbar(dev(x, unaligned), dev(w, unaligned), None if bias is None else dev(bias), y, M, N, K, cfg,
-                    relu=relu, split_k=split_k, workspace=ws)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
+    return run_ip("ip_fwd_xbar", x, w, bias, cfg_args, relu, split_k, unaligned)
 
 
 BIG = (40, 300, 2068, 64)     # 33 tiles, the last short; several workgroup tiles
@@ -115,30 +89,8 @@ def test_gaussian_boundary_aware(device, shape, bits, e):
     assert not bad.any(), (int(bad.sum()), float(np.abs(Sg - S).max()))
 
 
-NET = ('force_backward: true\n'
-       'layer {{ name: "x" type: "Input" top: "x" input_param {{ shape {{ dim: 37 dim: 100 }} }} }}\n'
-       'layer {{ name: "ip" type: "InnerProduct" bottom: "x" top: "y" {xbar} inner_product_param {{ num_output: 45 '
-       'weight_filler {{ type: "uniform" }} bias_filler {{ type: "uniform" }} }} }}\n'
-       'layer {{ name: "relu" type: "ReLU" bottom: "y" top: "y" }}\n')
-
-
 def _net(xbar="", options=None, x=None, w=None, b=None, dy=None):
-    """(y, dx, dw, db) of the three-layer net on the given blobs."""
-    import torch
-    from rramsim import caffe
-    caffe.set_stream_from_torch()
-    net = caffe.Net(NET.format(xbar=xbar), "train", options)
-    ps = net.params()
-    for t, a in ((net.blob("x"), x), (ps[0]["data"], w), (ps[1]["data"], b)):
-        t.copy_(torch.from_numpy(a).reshape(t.shape))
-    net.clear_param_diffs()
-    net.forward()
-    y = net.blob("y").cpu().numpy()
-    net.blob("y", diff=True).copy_(torch.from_numpy(dy))
-    net.backward()
-    out = (y, net.blob("x", diff=True).cpu().numpy(), ps[0]["diff"].cpu().numpy(), ps[1]["diff"].cpu().numpy())
-    net.close()
-    return out
+    return run_net(IP_NET.format(xbar=xbar), options, x, w, b, dy)
 
 
 @gpu

@@ -5,6 +5,7 @@ under every split and chunking, within the near-tie count on Gaussian inputs,
 through the InnerProduct layer, and refused where the header says so."""
 import numpy as np
 import pytest
+from _xbar_cases import IP_NET, adc_tile, dac_codes, grid, run_ip as run, run_net, same_bits
 
 gpu = pytest.mark.gpu
 
@@ -14,25 +15,17 @@ def ref_bs(x, w, bias, R, B, A, b, X, relu=False):
     x, w = x.astype(np.float64), w.astype(np.float64)
     cmax, qmax = 2 ** (b - 1) - 1, 2 ** (B - 1) - 1
     xs, step = float(np.float32(X)) / cmax, float(np.float32(A)) / qmax
-    c = np.clip(np.rint(x / float(np.float32(xs))), -cmax, cmax).astype(np.int64)
+    c = dac_codes(x, float(np.float32(xs)), cmax).astype(np.int64)
     S = np.zeros((x.shape[0], w.shape[0]), np.int64)
     near = np.zeros(S.shape, np.int64)
     clipped = False
     for k0 in range(0, x.shape[1], R):
         ct, wt = c[:, k0:k0 + R], w[:, k0:k0 + R]
         for j in range(b - 1):
-            u = np.sign(ct) * ((np.abs(ct) >> j) & 1)
-            r = (u @ wt.T) / step
-            margin = 1e-6 * (np.abs(u) @ np.abs(wt).T) / step
-            near += (np.abs(np.abs(r) % 1.0 - 0.5) <= margin) & (np.abs(r) < qmax + 1)
-            clipped |= bool((np.abs(np.rint(r)) > qmax).any())
-            S += np.clip(np.rint(r), -qmax, qmax).astype(np.int64) << j
+            q, n, cl = adc_tile(np.sign(ct) * ((np.abs(ct) >> j) & 1), wt, step, qmax)
+            S, near, clipped = S + (q << j), near + n, clipped | cl
     y = S * float(np.float32(step * xs)) + (0.0 if bias is None else bias.astype(np.float64))
     return (np.maximum(y, 0.0) if relu else y).astype(np.float32), S, near, clipped
-
-
-def grid(shape, seed, lo=-7, hi=7, scale=2.0 ** -3):
-    return (np.random.default_rng(seed).integers(lo, hi + 1, shape) * scale).astype(np.float32)
 
 
 def cfg_of(R, B, e, b, ex):
@@ -46,32 +39,6 @@ def half_codes(shape, seed, b, ex):
     return grid(shape, seed, -n, n, 2.0 ** (ex - 1))
 
 
-def run(fn, x, w, bias, cfg_args, relu=False, split_k=0, unaligned=False):
-    """fn = "ip_fwd_xbar_bs" or "ip_fwd_xbar" on device copies (unaligned: views one float past an allocation)."""
-    import torch
-    from rramsim import ops
-    M, K = x.shape
-    N = w.shape[0]
-    cfg = ops.xbar_cfg(*cfg_args)
-
-    def dev(a):
-        t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
-        v = t[1:] if unaligned else t[:-1]
-        v.copy_(torch.from_numpy(a.reshape(-1)))
-        return v.view(*a.shape)
-
-    y = torch.full((M, N), float("nan"), device="cuda")
-    ws = torch.empty(max(1, getattr(ops, fn + "_workspace")(M, N, K, cfg, split_k)), dtype=torch.uint8, device="cuda")
-    getattr(ops, fn)(dev(x), dev(w), None if bias is None else dev(bias), y, M, N, K, cfg, relu=relu,
-                     split_k=split_k, workspace=ws)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-def same_bits(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 MID, BIG = (33, 130, 96, 32), (40, 300, 2068, 64)
 # (M, N, K, R), adc_bits, log2(step), dac_bits, bias + relu, unaligned
 EXACT = [((1, 1, 1, 32), 8, -3, 2, False, False),       # one plane
@@ -79,7 +46,9 @@ EXACT = [((1, 1, 1, 32), 8, -3, 2, False, False),       # one plane
          (MID, 4, -2, 4, True, False),                  # the ADC clips
          ((5, 10, 50, 32), 8, -2, 3, False, True),      # short last tile, scalar loads
          ((70, 200, 300, 128), 12, -3, 5, False, False),
-         (BIG, 8, -2, 12, True, False)]                 # 33 tiles, two plane chunks, the finish kernel
+         (BIG, 8, -2, 12, True, False),                 # 33 tiles, two plane chunks, the finish kernel
+         ((5, 10, 50, 32), 8, -2, 8, False, True)]      # short last tile, scalar loads, the 7-plane chunk
+                                                        # (<scalar; p7>); last, so the ids above stay
 
 
 @gpu
@@ -133,33 +102,13 @@ def test_gaussian_boundary_aware(device, shape, B, e, b):
     assert (np.abs(Sg - S) <= 2 ** (b - 2) * near).all()  # a tie on the highest plane moves S by 2^(b-2); none: equal
 
 
-NET = ('force_backward: true\n'
-       'layer {{ name: "x" type: "Input" top: "x" input_param {{ shape {{ dim: 37 dim: 100 }} }} }}\n'
-       'layer {{ name: "ip" type: "InnerProduct" bottom: "x" top: "y" {xbar} inner_product_param {{ num_output: 45 '
-       'weight_filler {{ type: "uniform" }} bias_filler {{ type: "uniform" }} }} }}\n'
-       'layer {{ name: "relu" type: "ReLU" bottom: "y" top: "y" }}\n')
 CONV = ('layer {{ name: "x" type: "Input" top: "x" input_param {{ shape {{ dim: 4 dim: 5 dim: 6 dim: 6 }} }} }}\n'
         'layer {{ name: "conv" type: "Convolution" bottom: "x" top: "y" {xbar} convolution_param {{ num_output: 9 '
         'kernel_size: 3 pad: 1 }} }}\n')
 
 
 def _net(xbar, options, x, w, b, dy):
-    """(y, dx, dw, db) of the three-layer net on the given blobs."""
-    import torch
-    from rramsim import caffe
-    caffe.set_stream_from_torch()
-    net = caffe.Net(NET.format(xbar=xbar), "train", options)
-    ps = net.params()
-    for t, a in ((net.blob("x"), x), (ps[0]["data"], w), (ps[1]["data"], b)):
-        t.copy_(torch.from_numpy(a).reshape(t.shape))
-    net.clear_param_diffs()
-    net.forward()
-    y = net.blob("y").cpu().numpy()
-    net.blob("y", diff=True).copy_(torch.from_numpy(dy))
-    net.backward()
-    out = (y, net.blob("x", diff=True).cpu().numpy(), ps[0]["diff"].cpu().numpy(), ps[1]["diff"].cpu().numpy())
-    net.close()
-    return out
+    return run_net(IP_NET.format(xbar=xbar), options, x, w, b, dy)
 
 
 @gpu

@@ -6,7 +6,8 @@ under every split over K and every batch size; within the number of near-tie
 tiles on Gaussian inputs; and through the Convolution layer and the Net option."""
 import numpy as np
 import pytest
-from test_gpu_xbar import dev, grid, ref_xbar
+from _xbar_cases import dev, grid, run_net
+from test_gpu_xbar import ref_xbar
 
 gpu = pytest.mark.gpu
 
@@ -141,22 +142,7 @@ NET = ('force_backward: true\n'
 
 
 def _net(xbar, options, x, w, b, dy):
-    """(y, dx, dw, db) of the three-layer net on the given blobs."""
-    import torch
-    from rramsim import caffe
-    caffe.set_stream_from_torch()
-    net = caffe.Net(NET.format(xbar=xbar), "train", options)
-    ps = net.params()
-    for t, a in ((net.blob("x"), x), (ps[0]["data"], w), (ps[1]["data"], b)):
-        t.copy_(torch.from_numpy(a).reshape(t.shape))
-    net.clear_param_diffs()
-    net.forward()
-    y = net.blob("y").cpu().numpy()
-    net.blob("y", diff=True).copy_(torch.from_numpy(dy))
-    net.backward()
-    out = (y, net.blob("x", diff=True).cpu().numpy(), ps[0]["diff"].cpu().numpy(), ps[1]["diff"].cpu().numpy())
-    net.close()
-    return out
+    return run_net(NET.format(xbar=xbar), options, x, w, b, dy)
 
 
 @gpu
