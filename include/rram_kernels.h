@@ -730,6 +730,52 @@ int rram_ip_fwd_xbar_bs(const float* x, const float* w, const float* bias, float
 size_t rram_ip_fwd_xbar_bs_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
 int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                    int split_k, size_t ws_bytes, char* out, size_t cap);
+/* The bit-sliced-weight read-out of the same arrays (no reference counterpart;
+ * DESIGN §7.7): a cell stores cell_bits bits, a weight of weight_bits bits is
+ * spread over Ns = ceil((weight_bits - 1) / cell_bits) columns, every column
+ * has its own ADC conversion per tile and a shift-and-add combines the codes.
+ * Every operand is a small integer, so a tile's column sum is an exact int32
+ * (v_mfma_i32_32x32x32_i8).  The DAC is mandatory, dac_bits in [2, 8].  With
+ * cmax = 2^(dac_bits-1) - 1, dmax = 2^(weight_bits-1) - 1, qmax as above and
+ * xs = float(dac_range / cmax), ws = float(weight_range / dmax),
+ * kf = float((dac_range / cmax) * (weight_range / dmax) / (adc_range / qmax)),
+ * out_scale = float(adc_range / qmax), all computed in double:
+ *   c = clamp(rint(x / xs), +-cmax),  d = clamp(rint(w / ws), +-dmax),
+ *   d_s = sign(d) * ((|d| >> s * cell_bits) & (2^cell_bits - 1)), s = 0 .. Ns-1
+ *         (sign-magnitude; the top slice may be narrower),
+ *   p_{t,s} = sum over the tile's rows of c * d_s (int32, exact),
+ *   q_{t,s} = clamp(rint(float(p_{t,s}) * kf), +-qmax)   (half to even),
+ *   S = sum_t sum_s q_{t,s} << (s * cell_bits) (int32),
+ *   y = float(S) * out_scale + bias, ReLU.
+ * adc_range is the full scale of ONE SLICE's column sum in x * w units, the
+ * slice counted in units of ws (not scaled by its position).
+ * Refused (RRAM_EINVAL before the device is touched): everything
+ * rram_ip_fwd_xbar refuses, dac_bits outside [2, 8], slices NULL, weight_bits
+ * outside [2, 8], cell_bits outside [1, weight_bits - 1], a non-finite or
+ * non-positive weight_range, and ceil(K / rows) * qmax * sum_s 2^(s * cell_bits)
+ * >= 2^31.  M == 0 or N == 0 is RRAM_OK with no launch.
+ * The workspace (16-byte aligned) always holds the Ns int8 slice planes of the
+ * weights, written once per call: ceil(N / 128) * ceil(K / 32) * Ns * 4096
+ * bytes (Ns bytes per weight of the padded matrix).  Slices beyond 4 are cut
+ * into C = ceil(Ns / 4) chunks, a further factor of the grid beside the S
+ * splits over K: with S * C > 1 the int32 slabs add S * C * M * N * 4 bytes.
+ * rram_ip_fwd_xbar_ws_workspace gives the sum (split_k = 0: the most the
+ * planner would use); less is RRAM_EINVAL.  S is an integer: every split and
+ * every chunking give the same bits.  rram_ip_fwd_xbar_ws_kernel_ids (host
+ * only): xbar:pack_i8<vec|scalar>, xbar:pack_wslices<vec|scalar>,
+ * xbar:ip_ws<pPC>/sS/cC (PC = 4 slices per chunk), and xbar:finish when
+ * S * C > 1. */
+typedef struct {
+  int32_t weight_bits, cell_bits;
+  float weight_range;
+} rram_xbar_slices;
+int rram_ip_fwd_xbar_ws(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices, int relu,
+                        int split_k, void* ws, size_t ws_bytes, rram_stream_t stream);
+size_t rram_ip_fwd_xbar_ws_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                     int split_k);
+int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                   int x_align16, int w_align16, int split_k, size_t ws_bytes, char* out, size_t cap);
 /* The crossbar-tiled Convolution forward (no reference counterpart; DESIGN
  * §7.5): the array of group g holds the unrolled kernel, rows
  * k = (ci * kernel_h + i) * kernel_w + j (Caffe's im2col / weight-blob order),

@@ -31,6 +31,8 @@
 // array with the unrolled kernel as its rows: see the comment above the kernel.
 // The bit-serial read-out of the InnerProduct array (k_ip_xbar_bs)
 // converts every input bit plane on its own: see the comment above that kernel.
+// The bit-sliced-weight read-out (k_ip_xbar_ws) converts every
+// weight slice's column sum on its own, on int8 codes and the int32 MFMA.
 // The kernels are built from the shared pieces below; which kernel uses which,
 // and why k_conv_xbar keeps some text of its own, is above k_conv_xbar.
 #include <algorithm>
@@ -118,6 +120,8 @@ __device__ __forceinline__ int32_t adc_code(float p, float inv_step, float qmax)
 struct PackUnit {
   int g, h;
   char* row;
+  int64_t slab;  // tm * ksteps + ks: which [row tile][K-step] slab
+  int r;         // the row inside it
 };
 template <bool VEC>
 __device__ __forceinline__ PackUnit pack_unit(int64_t u, const float* __restrict__ x, int M, int K, int ksteps,
@@ -146,7 +150,7 @@ __device__ __forceinline__ PackUnit pack_unit(int64_t u, const float* __restrict
   }
   const int64_t tm = mrow / bm;
   const int row = static_cast<int>(mrow - tm * bm);
-  return {g, h, out + ((tm * ksteps + ks) * bm + row) * row_bytes};
+  return {g, h, out + ((tm * ksteps + ks) * bm + row) * row_bytes, tm * ksteps + ks, row};
 }
 
 // x [M][K] fp32 -> DAC -> bf16 terms in the K-step slabs k_ip_xbar copies to
@@ -519,6 +523,196 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
       }
   };
   pipeline(smem, T::STAGE, tile_span(z, P), P.spt, gload, compute, lstore, adc);
+
+  ip_store(S, P, P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr, m0, n0 + nw, lh);
+}
+
+// The bit-sliced-weight read-out: a cell stores cb bits, the
+// code d of a weight is spread over Ns columns, slice s holding d_s = sign(d) *
+// ((|d| >> s cb) & (2^cb - 1)); the ADC converts every slice's column sum of
+// every crossbar tile on its own and a shift-and-add combines the codes:
+//   S[m][n] = sum_t sum_s q_{t,s}[m][n] << (s cb) (int32),  y = float(S) * out_scale + bias.
+// The activations are their DAC codes c (dac_bits <= 8), so both operands are
+// int8 and a tile's column sum is an exact int32 on v_mfma_i32_32x32x32_i8: one
+// MFMA per product and K-step of 32, no split, no term order.
+//
+// Operands.  Lane (lr, lh) of either MFMA operand holds 16 bytes: the codes
+// k = 16 lh + j, j = 0 .. 15, of its row (which k of the step the matrix pipe
+// pairs with which does not matter as long as both operands agree, and a
+// tile's sum does not depend on the order).  k_xbar_pack_i8 writes the
+// activation codes as the LDS image of a K-step: [row tile][K-step][64 rows]
+// [48 B], a row = its two 16-byte halves + 16 B pad (3 units: coprime with the
+// 16 units of an LDS bank row, conflict-free ds_read_b128).  k_xbar_pack_wslices
+// reads the weights once per forward as fp32 and writes the Ns slice planes:
+// [column tile][K-step][slice][128 rows][32 B], the half h of row n at unit
+// h ^ ((n >> 3) & 1) (wslice_lds: 16 consecutive rows then cover the 16 bank
+// units once, without a pad, so a plane costs one byte per weight).  The
+// slices of a chunk lie next to each other, so a stage's weight fill is one
+// run of np * 4096 bytes.
+//
+// Work split.  A workgroup (4 waves) owns 64 rows x 128 columns for a range of
+// whole crossbar tiles and one chunk of up to PC slices; wave w owns all rows
+// x columns 32 w .. 32 w + 31: two 32 x 32 blocks, each with PC int32 sets
+// (one per slice of the chunk) and the int32 set S.  One activation fragment
+// serves all PC slices, one slice fragment both row blocks; the K loop has no
+// VALU work on operands.  The ADC at a tile boundary: convert, multiply by kf,
+// round, clamp, convert, shift-add by s cb into S; the sets are cleared through
+// the matrix pipe (zero_set, as in k_ip_xbar_bs).  More than PC slices are
+// chunks, a grid factor combined like K splits.  Both operands are copied as
+// they lie through registers into two LDS stages (pipeline).
+constexpr int QRB = 32 + 16;  // int8 code row bytes per K-step
+struct Wsl {
+  static constexpr int MI = 2, BM = 32 * MI;
+  static constexpr int A_B = BM * QRB;   // code bytes per K-step and row tile
+  static constexpr int A_U = A_B / 16;   // ... in 16-byte units, below the 256 threads
+  static constexpr int P_B = BN * KS;    // bytes of one slice plane per K-step and column tile
+  static_assert(A_U <= 256 && P_B == 256 * 16, "one unit per thread");
+};
+
+struct WsPlan : Plan {  // Core::step is out_scale; Plan::w is not read by the read-out kernel
+  const char* wplanes;  // the slice planes (the head of the caller's workspace)
+  int ns, cb;           // slices of a weight, bits of a cell
+  int chunks;           // ceil(ns / PC)
+  float kf;             // partial sum -> ADC steps
+};
+
+// x [M][K] fp32 -> two's-complement int8 DAC codes clamp(rint(x / xs), +-cmax)
+// in the K-step slabs k_ip_xbar_ws copies to LDS (zero past M and K, zero pad).
+// One thread per unit: 8 activations in, 8 bytes out.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_xbar_pack_i8(const float* __restrict__ x, int M, int K, char* __restrict__ out,
+                                                      int ksteps, int64_t units, float xs, float cmax) {
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    float v[8];
+    const PackUnit U = pack_unit<VEC>(u, x, M, K, ksteps, out, Wsl::BM, QRB, v);
+    uint32_t cw[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = static_cast<int>(__builtin_amdgcn_fmed3f(__builtin_rintf(v[j] / xs), -cmax, cmax));
+      cw[j >> 2] |= (static_cast<uint32_t>(c) & 0xFFu) << (8 * (j & 3));
+    }
+    *reinterpret_cast<uint2*>(U.row + U.h * 16 + U.g * 8) = make_uint2(cw[0], cw[1]);
+    if (U.g == 1 && U.h == 1) *reinterpret_cast<uint4*>(U.row + 32) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// where half h (16 k) of weight row `row` lies in a slice plane [128 rows][32 B]:
+// k_xbar_pack_wslices writes through this and k_ip_xbar_ws reads through it
+__device__ __forceinline__ int wslice_lds(int row, int h) { return row * KS + ((h ^ ((row >> 3) & 1)) << 4); }
+
+// w [N][K] fp32 -> codes d = clamp(rint(w / ws), +-dmax) -> the ns sign-magnitude
+// slices of cb bits as int8 planes [column tile][K-step][slice][128 rows][32 B]
+// (zero past N and K).  One thread per unit: 8 weights in, 8 bytes out per slice.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_xbar_pack_wslices(const float* __restrict__ w, int N, int K,
+                                                           char* __restrict__ out, int ksteps, int64_t units, float ws,
+                                                           float dmax, int ns, int cb) {
+  const int mask = (1 << cb) - 1;
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    float v[8];
+    const PackUnit U = pack_unit<VEC>(u, w, N, K, ksteps, out, BN, KS, v);
+    int mag[8];
+    bool neg[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = __builtin_amdgcn_fmed3f(__builtin_rintf(v[j] / ws), -dmax, dmax);
+      mag[j] = static_cast<int>(__builtin_fabsf(d));
+      neg[j] = d < 0.0f;
+    }
+    char* dst = out + U.slab * ns * Wsl::P_B + wslice_lds(U.r, U.h) + U.g * 8;
+    for (int s = 0; s < ns; ++s) {
+      uint32_t dw[2] = {0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int m = (mag[j] >> (s * cb)) & mask;
+        dw[j >> 2] |= (static_cast<uint32_t>(neg[j] ? -m : m) & 0xFFu) << (8 * (j & 3));
+      }
+      *reinterpret_cast<uint2*>(dst + s * Wsl::P_B) = make_uint2(dw[0], dw[1]);
+    }
+  }
+}
+
+template <int PC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_ip_xbar_ws(WsPlan P) {
+  typedef Wsl T;
+  typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+  typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
+  constexpr int STAGE_B = T::A_B + PC * T::P_B;
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_B];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const int id = xcd_tile_id(blockIdx.x, gridDim.x);
+  const int tm = __builtin_amdgcn_readfirstlane(id % P.tiles_m);
+  const int tn = __builtin_amdgcn_readfirstlane((id / P.tiles_m) % P.tiles_n);
+  const int zc = __builtin_amdgcn_readfirstlane(id / (P.tiles_m * P.tiles_n));  // chunk * split + z: the slab
+  const int z = zc % P.split;
+  const int j0 = (zc / P.split) * PC;      // the chunk's first slice
+  const int np = min(PC, P.ns - j0);       // ... and how many it has
+  const int m0 = tm * T::BM, n0 = tn * BN;
+
+  // this thread's pieces of a K-step, copied as they lie: one 16-byte unit of the
+  // codes (the first A_U threads) and one of each of the chunk's np slice planes
+  const char* asrc = P.apack + (int64_t)tm * P.ksteps * T::A_B + tid * 16;
+  const char* bsrc = P.wplanes + ((int64_t)tn * P.ksteps * P.ns + j0) * T::P_B + tid * 16;
+  uint4 ra, rb[PC];
+  auto gload = [&](int s) {
+    if (tid < T::A_U) ra = *reinterpret_cast<const uint4*>(asrc + (int64_t)s * T::A_B);
+#pragma unroll
+    for (int j = 0; j < PC; ++j)
+      if (j < np) rb[j] = *reinterpret_cast<const uint4*>(bsrc + ((int64_t)s * P.ns + j) * T::P_B);
+  };
+  auto lstore = [&](char* st) {
+    if (tid < T::A_U) *reinterpret_cast<uint4*>(st + tid * 16) = ra;
+#pragma unroll
+    for (int j = 0; j < PC; ++j)
+      if (j < np) *reinterpret_cast<uint4*>(st + T::A_B + j * T::P_B + tid * 16) = rb[j];
+  };
+
+  // a cleared set comes out of the matrix pipe (0 * 0 + 0, the addend an inline
+  // constant), as in k_ip_xbar_bs: no zeros are written as vector registers
+  auto zero_set = [&]() {
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(i32x4{0, 0, 0, 0}, i32x4{0, 0, 0, 0}, i32x16{}, 0, 0, 0);
+  };
+  i32x16 acc[T::MI][PC];  // the current crossbar tile's column sums, one set per slice
+  int32_t S[T::MI][16];   // the shift-and-add of the ADC codes
+#pragma unroll
+  for (int i = 0; i < T::MI; ++i) {
+#pragma unroll
+    for (int j = 0; j < PC; ++j) acc[i][j] = zero_set();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S[i][r] = 0;
+  }
+
+  const int nw = 32 * wave + lr;  // this lane's weight row (output column) inside the tile
+  const int boff = T::A_B + wslice_lds(nw, lh);
+  auto compute = [&](const char* st) {
+    i32x4 a[T::MI];
+#pragma unroll
+    for (int i = 0; i < T::MI; ++i) a[i] = *reinterpret_cast<const i32x4*>(st + (i * 32 + lr) * QRB + lh * 16);
+#pragma unroll
+    for (int j = 0; j < PC; ++j)
+      if (j < np) {
+        const i32x4 b = *reinterpret_cast<const i32x4*>(st + boff + j * T::P_B);
+#pragma unroll
+        for (int i = 0; i < T::MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b, acc[i][j], 0, 0, 0);
+      }
+  };
+  // the ADC at a tile boundary, per slice: codes shifted by the slice's position into S, the sets cleared
+  // (every set of the pass is converted; a slice past np has stayed 0 and adds 0)
+  auto adc = [&]() {
+#pragma unroll
+    for (int i = 0; i < T::MI; ++i)
+#pragma unroll
+      for (int j = 0; j < PC; ++j) {
+        const int sh = (j0 + j) * P.cb;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) S[i][r] += adc_code(static_cast<float>(acc[i][j][r]), P.kf, P.qmax) * (1 << sh);
+        acc[i][j] = zero_set();
+      }
+  };
+  pipeline(smem, STAGE_B, tile_span(z, P), P.spt, gload, compute, lstore, adc);
 
   ip_store(S, P, P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr, m0, n0 + nw, lh);
 }
@@ -1024,6 +1218,116 @@ int ip_fwd(bool serial, const float* x, const float* w, const float* bias, float
   return launch_finish(serial ? "ip_fwd_xbar_bs finish" : "ip_fwd_xbar finish", P, slabs, M, N, 1, s);
 }
 
+// The bit-sliced-weight read-out's checks (host only).  Both operands must fit
+// int8, and S (so every partial slab too) int32: |S| <= ntiles * qmax * sum_s 2^(s cb).
+constexpr int WS_PC = 4;  // slices per chunk: the one k_ip_xbar_ws instantiation
+int slices_of(const rram_xbar_slices& sl) { return (sl.weight_bits - 1 + sl.cell_bits - 1) / sl.cell_bits; }
+
+int ws_check(int M, int N, int K, const rram_xbar_cfg* c, const rram_xbar_slices* sl, int transpose) {
+  const int rc = check(M, N, K, c, transpose);
+  if (rc) return rc;
+  RRAM_REQUIRE(c->dac_bits >= 2 && c->dac_bits <= 8, "ip_fwd_xbar_ws: dac_bits %d outside [2, 8]", c->dac_bits);
+  RRAM_REQUIRE(sl != nullptr, "ip_fwd_xbar_ws: slices is NULL");
+  RRAM_REQUIRE(sl->weight_bits >= 2 && sl->weight_bits <= 8, "ip_fwd_xbar_ws: weight_bits %d outside [2, 8]",
+               sl->weight_bits);
+  RRAM_REQUIRE(sl->cell_bits >= 1 && sl->cell_bits <= sl->weight_bits - 1,
+               "ip_fwd_xbar_ws: cell_bits %d outside [1, weight_bits - 1]", sl->cell_bits);
+  RRAM_REQUIRE(std::isfinite(sl->weight_range) && sl->weight_range > 0.0f,
+               "ip_fwd_xbar_ws: weight_range must be finite and > 0");
+  const int64_t ntiles = (K + c->rows - 1) / c->rows, qmax = (1 << (c->adc_bits - 1)) - 1;
+  int64_t weight = 0;
+  for (int s = 0; s < slices_of(*sl); ++s) weight += 1ll << (s * sl->cell_bits);
+  RRAM_REQUIRE(ntiles * qmax * weight < (1ll << 31),
+               "ip_fwd_xbar_ws: %lld tiles x qmax %lld x slice weights %lld overflows int32", (long long)ntiles,
+               (long long)qmax, (long long)weight);
+  return RRAM_OK;
+}
+
+// The plan of a shape; ws_bytes is the caller's whole workspace, of which the
+// slice planes take plane_bytes first and the planner's slabs the rest.  The
+// chunk count is folded into the planner's workgroup count and slab size.
+size_t make_ws_plan(int M, int N, int K, const rram_xbar_cfg& c, const rram_xbar_slices& sl, int split_k,
+                    size_t ws_bytes, WsPlan& P) {
+  P = WsPlan{};
+  P.M = M, P.N = N, P.K = K;
+  P.ns = slices_of(sl), P.cb = sl.cell_bits;
+  P.chunks = (P.ns + WS_PC - 1) / WS_PC;
+  P.tiles_m = (M + Wsl::BM - 1) / Wsl::BM;
+  P.tiles_n = (N + BN - 1) / BN;
+  const size_t plane_bytes = (size_t)P.tiles_n * ((K + KS - 1) / KS) * P.ns * Wsl::P_B;
+  plan_core(P, K, c, (int64_t)P.tiles_m * P.tiles_n * P.chunks, (size_t)M * N * sizeof(int32_t) * P.chunks, split_k,
+            ws_bytes > plane_bytes ? ws_bytes - plane_bytes : 0);
+  const double cmax = (1 << (c.dac_bits - 1)) - 1, dmax = (1 << (sl.weight_bits - 1)) - 1;
+  P.kf = static_cast<float>(static_cast<double>(c.dac_range) / cmax * (static_cast<double>(sl.weight_range) / dmax) /
+                            (static_cast<double>(c.adc_range) / P.qmax));
+  return plane_bytes;
+}
+
+size_t ws_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int split_k) {
+  if (ws_check(M, N, K, cfg, sl, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
+  WsPlan P;
+  const size_t plane_bytes = make_ws_plan(M, N, K, *cfg, *sl, split_k, ~static_cast<size_t>(0), P);
+  return plane_bytes + part_bytes(P.split * P.chunks, (int64_t)M * N);
+}
+
+int ws_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int transpose,
+           const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int relu, int split_k, void* ws, size_t ws_bytes,
+           rram_stream_t st) {
+  const char* who = "ip_fwd_xbar_ws";
+  const int rc0 = ws_check(M, N, K, cfg, sl, transpose);
+  if (rc0) return rc0;
+  RRAM_REQUIRE(split_k >= 0, "%s: negative split_k", who);
+  if (M == 0 || N == 0) return RRAM_OK;
+  RRAM_REQUIRE(x && w && y, "%s: NULL", who);
+  RRAM_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, "%s: workspace not 16-byte aligned", who);
+  WsPlan P;
+  const size_t plane_bytes = make_ws_plan(M, N, K, *cfg, *sl, split_k, ws != nullptr ? ws_bytes : 0, P);
+  const int slabs = P.split * P.chunks;
+  const int rcw = require_ws(who, ws, ws_bytes, plane_bytes + part_bytes(slabs, (int64_t)M * N), P.split, P.chunks);
+  if (rcw) return rcw;
+  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * slabs < (1ll << 31), "%s: grid too large", who);
+  hipStream_t s = as_stream(st);
+  const Steps dac = steps_of(*cfg);
+
+  if (!plan_note("xbar:pack_i8<%s>", al16(x, K) ? "vec" : "scalar")) {
+    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * Wsl::A_B;
+    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
+    RRAM_REQUIRE(pb != nullptr, "%s: packed-code buffer allocation failed", who);
+    P.apack = pb;
+    const int64_t units = (int64_t)P.tiles_m * Wsl::BM * P.ksteps * 4;
+    by_vec(al16(x, K), [&](auto V) {
+      hipLaunchKernelGGL(k_xbar_pack_i8<decltype(V)::value>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
+                         P.ksteps, units, dac.dac_xs, dac.dac_qmax);
+    });
+    const int rc = launch_status("ip_fwd_xbar_ws pack");
+    if (rc) return rc;
+  }
+  P.wplanes = static_cast<const char*>(ws);
+  if (!plan_note("xbar:pack_wslices<%s>", al16(w, K) ? "vec" : "scalar")) {
+    const float dmax = static_cast<float>((1 << (sl->weight_bits - 1)) - 1);
+    const float wsc = static_cast<float>(static_cast<double>(sl->weight_range) / dmax);
+    const int64_t units = (int64_t)P.tiles_n * BN * P.ksteps * 4;
+    by_vec(al16(w, K), [&](auto V) {
+      hipLaunchKernelGGL(k_xbar_pack_wslices<decltype(V)::value>, dim3(stream_blocks(units)), dim3(256), 0, s, w, N, K,
+                         static_cast<char*>(ws), P.ksteps, units, wsc, dmax, P.ns, P.cb);
+    });
+    const int rc = launch_status("ip_fwd_xbar_ws weight pack");
+    if (rc) return rc;
+  }
+  P.w = w;
+  P.bias = bias;
+  P.y = y;
+  P.part = slabs > 1 ? reinterpret_cast<int32_t*>(static_cast<char*>(ws) + plane_bytes) : nullptr;
+  P.relu = relu;
+  if (!plan_note("xbar:ip_ws<p%d>/s%d/c%d", WS_PC, P.split, P.chunks)) {
+    hipLaunchKernelGGL(k_ip_xbar_ws<WS_PC>, dim3(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs)), dim3(256), 0, s,
+                       P);
+    const int rc = launch_status(who);
+    if (rc) return rc;
+  }
+  return launch_finish("ip_fwd_xbar_ws finish", P, slabs, M, N, 1, s);
+}
+
 }  // namespace xb
 }  // namespace
 }  // namespace rram
@@ -1064,6 +1368,27 @@ int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg
   rram::PlanScope sc;
   const int rc = rram_ip_fwd_xbar_bs(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
                                      0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
+  return rc ? rc : rram::copy_text(sc.text, out, cap);
+}
+
+size_t rram_ip_fwd_xbar_ws_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                     int split_k) {
+  return rram::xb::ws_workspace(M, N, K, cfg, slices, split_k);
+}
+
+int rram_ip_fwd_xbar_ws(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices, int relu,
+                        int split_k, void* ws, size_t ws_bytes, rram_stream_t st) {
+  return rram::xb::ws_fwd(x, w, bias, y, M, N, K, transpose, cfg, slices, relu, split_k, ws, ws_bytes, st);
+}
+
+int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                   int x_align16, int w_align16, int split_k, size_t ws_bytes, char* out,
+                                   size_t cap) {
+  using rram::xb::fake_ptr;
+  rram::PlanScope sc;
+  const int rc = rram_ip_fwd_xbar_ws(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
+                                     slices, 0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

@@ -142,11 +142,37 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
 // ("rows,adc_bits,adc_range[,dac_bits,dac_range[,bit_serial]]", handed down as
 // rram_crossbar to layers without the message).  False: neither is set.
 // *bit_serial: the bit-serial read-out (rram_ip_fwd_xbar_bs) is asked for.
-static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c, bool* bit_serial) {
+// sl->weight_bits != 0: the bit-sliced-weight read-out (rram_ip_fwd_xbar_ws) is
+// asked for, by crossbar_param { weight_slices { weight_bits cell_bits
+// weight_range } } or, for a layer with a crossbar and no weight_slices of its
+// own, the Net option `crossbar_slices` ("weight_bits,cell_bits,weight_range",
+// handed down as rram_crossbar_slices).
+static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c, bool* bit_serial,
+                          rram_xbar_slices* sl) {
   const Msg* xp = lp.sub("crossbar_param");
   *bit_serial = false;
+  *sl = rram_xbar_slices{0, 0, 0.0f};
   if (xp == nullptr && !lp.has("rram_crossbar")) return false;
   *c = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
+  const Msg* sp = xp != nullptr ? xp->sub("weight_slices") : nullptr;
+  if (sp != nullptr) {
+    sl->weight_bits = static_cast<int32_t>(sp->integer("weight_bits", 0));
+    sl->cell_bits = static_cast<int32_t>(sp->integer("cell_bits", 0));
+    sl->weight_range = static_cast<float>(sp->num("weight_range", 0.0));
+    CAFFE_CHECK(sl->weight_bits != 0, name << ": weight_slices wants weight_bits");
+  } else if (lp.has("rram_crossbar_slices")) {
+    std::vector<double> v;
+    std::stringstream ss(lp.str("rram_crossbar_slices"));
+    std::string t;
+    try {
+      while (std::getline(ss, t, ',')) v.push_back(std::stod(t));
+    } catch (const std::exception&) {
+      v.clear();
+    }
+    CAFFE_CHECK(v.size() == 3 && v[0] != 0.0,
+                name << ": option crossbar_slices wants weight_bits,cell_bits,weight_range");
+    *sl = rram_xbar_slices{static_cast<int32_t>(v[0]), static_cast<int32_t>(v[1]), static_cast<float>(v[2])};
+  }
   if (xp != nullptr) {
     c->rows = static_cast<int32_t>(xp->integer("rows", 0));
     c->adc_bits = static_cast<int32_t>(xp->integer("adc_bits", 0));
@@ -193,8 +219,10 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom
               "Convolution: channels/num_output must be divisible by group");
   bias_term_ = cp.boolean("bias_term", true);
   bool bit_serial = false;
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial);
+  rram_xbar_slices slices{};
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial, &slices);
   CAFFE_CHECK(!bit_serial, this->name() << ": bit_serial is not served for Convolution");
+  CAFFE_CHECK(slices.weight_bits == 0, this->name() << ": weight_slices is not served for Convolution");
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan
     // query for one image (before any blob is allocated: no device is touched)
@@ -427,6 +455,24 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
   axis_ = static_cast<int>(ip.integer("axis", 1));
   if (axis_ < 0) axis_ += bottom[0]->num_axes();
   K_ = static_cast<int>(bottom[0]->count(axis_));
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_, &slices_);
+  if (xbar_on_) {
+    // the kernel library's own checks of the configuration, on a host-only plan query
+    // (the bit-serial and bit-sliced ones with the workspace their chunks and planes need;
+    // before any blob is allocated: no device is touched)
+    CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
+    CAFFE_CHECK(!(xbar_ws() && xbar_bs_), this->name() << ": weight_slices with bit_serial is not served");
+    char id[8];
+    const int rc = xbar_ws() ? rram_ip_fwd_xbar_ws_kernel_ids(
+                                   1, N_, K_, &xbar_, &slices_, 1, 1, 0,
+                                   std::max<size_t>(1, rram_ip_fwd_xbar_ws_workspace(1, N_, K_, &xbar_, &slices_, 0)),
+                                   id, sizeof id)
+                   : xbar_bs_ ? rram_ip_fwd_xbar_bs_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0,
+                                                               rram_ip_fwd_xbar_bs_workspace(1, N_, K_, &xbar_, 0), id,
+                                                               sizeof id)
+                              : rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id);
+    CAFFE_CHECK(rc > 0, this->name() << ": crossbar_param: " << rram_last_error());
+  }
   this->blobs_.clear();
   this->blobs_.push_back(std::make_shared<Blob<Dtype>>(
       transpose_ ? std::vector<int>{K_, N_} : std::vector<int>{N_, K_}));
@@ -437,18 +483,6 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
     FillBlob(this->blobs_[1].get(), ip.sub_or_empty("bias_filler"), seed, 1);
   }
   this->param_propagate_down_.assign(this->blobs_.size(), true);
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_);
-  if (xbar_on_) {
-    // the kernel library's own checks of the configuration, on a host-only plan query
-    // (the bit-serial one with the workspace its plane chunks need)
-    CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
-    char id[8];
-    const int rc = xbar_bs_ ? rram_ip_fwd_xbar_bs_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0,
-                                                             rram_ip_fwd_xbar_bs_workspace(1, N_, K_, &xbar_, 0), id,
-                                                             sizeof id)
-                            : rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id);
-    CAFFE_CHECK(rc > 0, this->name() << ": crossbar_param: " << rram_last_error());
-  }
 }
 
 template <typename Dtype>
@@ -486,10 +520,17 @@ void InnerProductLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bott
     const Dtype* x = bottom[0]->gpu_data();
     Dtype* y = top[0]->mutable_gpu_data();
     const auto fwd = xbar_bs_ ? rram_ip_fwd_xbar_bs : rram_ip_fwd_xbar;
-    for (int g = 0; g < groups_; ++g)
-      RRAM_CALL(fwd(x + (int64_t)g * Mg * K_, w + g * group_stride_[0], b ? b + g * group_stride_[1] : b,
-                    y + (int64_t)g * Mg * N_, Mg, N_, K_, 0, &xbar_, fused_relu ? 1 : 0, 0, ws, Caffe::workspace_size(),
-                    Caffe::stream()));
+    for (int g = 0; g < groups_; ++g) {
+      const Dtype *xg = x + (int64_t)g * Mg * K_, *wg = w + g * group_stride_[0];
+      const Dtype* bg = b ? b + g * group_stride_[1] : b;
+      Dtype* yg = y + (int64_t)g * Mg * N_;
+      if (xbar_ws())  // the group's weights are sliced into the workspace by the call itself
+        RRAM_CALL(rram_ip_fwd_xbar_ws(xg, wg, bg, yg, Mg, N_, K_, 0, &xbar_, &slices_, fused_relu ? 1 : 0, 0, ws,
+                                      Caffe::workspace_size(), Caffe::stream()));
+      else
+        RRAM_CALL(fwd(xg, wg, bg, yg, Mg, N_, K_, 0, &xbar_, fused_relu ? 1 : 0, 0, ws, Caffe::workspace_size(),
+                      Caffe::stream()));
+    }
     return;
   }
   if (groups_ > 1) {  // map groups: no packed-row shortcut (rram_ip_fwd_groups has no rows form)

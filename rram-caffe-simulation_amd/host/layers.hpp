@@ -120,6 +120,7 @@ class InnerProductLayer : public Layer<Dtype> {
   size_t ws_request() const {
     const size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
     if (!xbar_on_) return f32;
+    if (xbar_ws()) return std::max(f32, rram_ip_fwd_xbar_ws_workspace(M_ / groups_, N_, K_, &xbar_, &slices_, 0));
     const auto need = xbar_bs_ ? rram_ip_fwd_xbar_bs_workspace : rram_ip_fwd_xbar_workspace;
     return std::max(f32, need(M_ / groups_, N_, K_, &xbar_, 0));
   }
@@ -128,6 +129,10 @@ class InnerProductLayer : public Layer<Dtype> {
   // rram_ip_fwd_xbar_bs, one conversion per input bit plane), the backward unchanged
   bool xbar_on_ = false, xbar_bs_ = false;
   rram_xbar_cfg xbar_{};
+  // weight_slices (or the Net option `crossbar_slices`): the bit-sliced-weight
+  // read-out rram_ip_fwd_xbar_ws, one conversion per weight slice (weight_bits 0: not asked for)
+  rram_xbar_slices slices_{};
+  bool xbar_ws() const { return slices_.weight_bits != 0; }
   uint64_t in_rows_key_ = 0;  // the packed-row companion this layer reads (Reshape; 0: none)
   // set_map_groups: the batch rows are groups_ groups of M_ / groups_ rows,
   // group g reading copy g of a faulted blob (nullptr: the layer's own blob)

@@ -194,6 +194,10 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
     // option crossbar_conv: the same for every Convolution layer
     if (type == "Convolution" && options.has("crossbar_conv") && lp.sub("crossbar_param") == nullptr)
       lp.set("rram_crossbar", options.str("crossbar_conv"));
+    // option crossbar_slices: every such layer that has a crossbar and no weight_slices of its own
+    // (read_crossbar; a Convolution layer refuses it)
+    if ((type == "InnerProduct" || type == "Convolution") && options.has("crossbar_slices"))
+      lp.set("rram_crossbar_slices", options.str("crossbar_slices"));
     auto layer = LayerRegistry<Dtype>::CreateLayer(lp);
     layer->layer_id = static_cast<uint32_t>(lid);
     const std::string lname = lp.str("name");

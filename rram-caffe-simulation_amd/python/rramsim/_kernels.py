@@ -90,6 +90,11 @@ class XbarCfg(C.Structure):
                 ("dac_bits", C.c_int32), ("dac_range", C.c_float)]
 
 
+class XbarSlices(C.Structure):
+    """rram_xbar_slices: bits of a weight code, bits of a cell, the weight range (bit-sliced-weight read-out)."""
+    _fields_ = [("weight_bits", C.c_int32), ("cell_bits", C.c_int32), ("weight_range", C.c_float)]
+
+
 # (name, restype, argtypes) for every symbol of include/rram_kernels.h
 P, I, I64, U32, U64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -178,6 +183,9 @@ SIGNATURES = {
     "rram_ip_fwd_xbar_bs": (I, [P, P, P, P, I, I, I, I, P, I, I, P, SZ, P]),
     "rram_ip_fwd_xbar_bs_workspace": (SZ, [I, I, I, P, I]),
     "rram_ip_fwd_xbar_bs_kernel_ids": (I, [I, I, I, P, I, I, I, SZ, C.c_char_p, SZ]),
+    "rram_ip_fwd_xbar_ws": (I, [P, P, P, P, I, I, I, I, P, P, I, I, P, SZ, P]),
+    "rram_ip_fwd_xbar_ws_workspace": (SZ, [I, I, I, P, P, I]),
+    "rram_ip_fwd_xbar_ws_kernel_ids": (I, [I, I, I, P, P, I, I, I, SZ, C.c_char_p, SZ]),
     "rram_conv2d_fwd_xbar": (I, [P, P, P, P, P, P, I, I, P, SZ, P]),
     "rram_conv2d_fwd_xbar_workspace": (SZ, [P, P, I]),
     "rram_conv2d_fwd_xbar_kernel_ids": (I, [P, P, I, I, I, SZ, C.c_char_p, SZ]),

@@ -477,6 +477,30 @@ def ip_fwd_xbar_bs_kernel_ids(M, N, K_, cfg, x_align16=True, w_align16=True, spl
                      split_k, int(ws_bytes))
 
 
+def xbar_slices(weight_bits, cell_bits, weight_range):
+    """rram_xbar_slices of the bit-sliced-weight read-out (ip_fwd_xbar_ws)."""
+    return K.XbarSlices(weight_bits, cell_bits, weight_range)
+
+
+def ip_fwd_xbar_ws(x, w, bias, y, M, N, K_, cfg, slices, transpose=False, relu=False, split_k=0, workspace=None):
+    """rram_ip_fwd_xbar_ws: the bit-sliced-weight read-out on int8 codes, one ADC conversion per weight slice and
+    crossbar tile (cfg.dac_bits in [2, 8]; cfg.adc_range is one slice's full scale; the workspace always holds
+    the slice planes: ip_fwd_xbar_ws_workspace; split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_fwd_xbar_ws(_p(x), _p(w), _p(bias), _p(y), M, N, K_, int(transpose), C.byref(cfg),
+                                       C.byref(slices), int(relu), split_k, _p(workspace), wsb, _stream()),
+            "ip_fwd_xbar_ws")
+
+
+def ip_fwd_xbar_ws_workspace(M, N, K_, cfg, slices, split_k=0):
+    return _lib().rram_ip_fwd_xbar_ws_workspace(M, N, K_, C.byref(cfg), C.byref(slices), split_k)
+
+
+def ip_fwd_xbar_ws_kernel_ids(M, N, K_, cfg, slices, x_align16=True, w_align16=True, split_k=0, ws_bytes=0):
+    return _id_lines(_lib().rram_ip_fwd_xbar_ws_kernel_ids, M, N, K_, C.byref(cfg), C.byref(slices), int(x_align16),
+                     int(w_align16), split_k, int(ws_bytes))
+
+
 def conv_fwd_xbar(d, x, w, bias, y, cfg, relu=False, split_k=0, workspace=None):
     """rram_conv2d_fwd_xbar: y = the ADC read-out of conv(x, w) from crossbars of cfg.rows rows of the
     unrolled kernel (d: a conv_desc; split_k 0: planner)."""

@@ -4,11 +4,17 @@ beside rram_ip_fwd on the fc6 / fc7 / CIFAR ip1 shapes, or with --conv
 rram_conv2d_fwd_xbar beside rram_conv2d_fwd on AlexNet conv2 / conv3, VGG11
 conv2 / conv8 and a GoogLeNet 1x1, or with --serial the bit-serial
 rram_ip_fwd_xbar_bs beside rram_ip_fwd_xbar with the same DAC (dac_bits 4 and 8)
-on the InnerProduct shapes.  Call times from device events (every launch
+on the InnerProduct shapes, or with --sliced the bit-sliced-weight
+rram_ip_fwd_xbar_ws (weight_bits 8, cell_bits 2 and 1) beside rram_ip_fwd_xbar
+with the same 8-bit DAC.  Call times from device events (every launch
 of the call included), the two alternated in one process, the median and range
 of REPS windows of ITERS calls each.
 
-    python scripts/xbar_bench.py [--conv | --serial] [out.txt]
+    python scripts/xbar_bench.py [--conv | --serial | --sliced] [out.txt]
+
+--sliced --shape=fc6 --cells=2 keeps one shape and one cell width, so that a
+kernel trace of the run (per-kernel totals) gives the weight pack's share of
+that call.
 """
 import sys
 from pathlib import Path
@@ -98,6 +104,31 @@ def serial_rows():
     return lines
 
 
+def sliced_rows(shape=None, cells=None):
+    lines = ["shape  M x N x K  R B b wb cb | sliced us (min..max) ids | parallel xbar us (min..max) ids | ratio | "
+             "MFMA count ratio Ns / 6 | sliced share of 416.7 TFLOP/s"]
+    for name, M, N, K, R, B in SHAPES:
+        for cb in (2, 1):
+            if (shape and shape not in name) or (cells and cells != cb):
+                continue
+            g = torch.Generator(device="cuda").manual_seed(1)
+            x = torch.randn(M, K, device="cuda", generator=g)
+            w = torch.randn(N, K, device="cuda", generator=g) * K ** -0.5
+            bias = torch.randn(N, device="cuda", generator=g)
+            y = torch.empty(M, N, device="cuda")
+            cfg, sl = ops.xbar_cfg(R, B, 4.0, 8, 4.0), ops.xbar_slices(8, cb, 4.0 * K ** -0.5)
+            wss = torch.empty(ops.ip_fwd_xbar_ws_workspace(M, N, K, cfg, sl), dtype=torch.uint8, device="cuda")
+            wsx = torch.empty(max(1, ops.ip_fwd_xbar_workspace(M, N, K, cfg)), dtype=torch.uint8, device="cuda")
+            fs = lambda: ops.ip_fwd_xbar_ws(x, w, bias, y, M, N, K, cfg, sl, relu=True, workspace=wss)  # noqa: E731
+            fx = lambda: ops.ip_fwd_xbar(x, w, bias, y, M, N, K, cfg, relu=True, workspace=wsx)         # noqa: E731
+            line = row(f"{name}  {M} x {N} x {K}  {R} {B} 8 8 {cb}", fs, fx,
+                       ops.ip_fwd_xbar_ws_kernel_ids(M, N, K, cfg, sl, ws_bytes=wss.numel()),
+                       ops.ip_fwd_xbar_kernel_ids(M, N, K, cfg, ws_bytes=wsx.numel()), 2.0 * M * N * K)
+            head, share = line.rsplit(" | ", 1)
+            lines.append(f"{head} | {-(-7 // cb) / 6:.2f} | {share}")
+    return lines
+
+
 def conv_rows():
     lines = ["shape  x -> Cout k/pad/group  R B | xbar us (min..max) ids | plain us (min..max) ids | ratio | "
              "xbar share of 416.7 TFLOP/s"]
@@ -123,7 +154,10 @@ def main():
     assert torch.cuda.is_available(), "needs a GPU"
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     args = [a for a in sys.argv[1:] if a not in flags]
+    opt = dict(f[2:].split("=", 1) for f in flags if "=" in f)
     rows = conv_rows if "--conv" in flags else serial_rows if "--serial" in flags else ip_rows
+    if "--sliced" in flags:
+        rows = lambda: sliced_rows(opt.get("shape"), int(opt.get("cells", 0)))  # noqa: E731
     text = "\n".join(rows()) + "\n"
     print(text, end="")
     if args:
