@@ -803,6 +803,31 @@ size_t rram_conv2d_fwd_xbar_workspace(const rram_conv_desc* d, const rram_xbar_c
 int rram_conv2d_fwd_xbar_kernel_ids(const rram_conv_desc* d, const rram_xbar_cfg* cfg, int x_align16, int w_align16,
                                     int split_k, size_t ws_bytes, char* out, size_t cap);
 
+/* The transposed read-out of the same arrays: the InnerProduct input gradient
+ * (no reference counterpart).  The error is propagated through
+ * the array read the other way: dy' (dy through the DAC of cfg, as x above)
+ * drives the columns, the currents are summed along the rows.  cfg is this
+ * read's own; cfg->rows is the number of array COLUMNS C one read sums over,
+ * so the N axis of W [N][K] is cut into ceil(N / C) tiles (the last may be
+ * short).  Per tile p_t[m][k] = sum dy'[m][n] W[n][k] in fp32 from zero (the
+ * forward's product order), q_t = clamp(rint(p_t / step), +-qmax), S = sum_t
+ * q_t as int32, dx = float(S) * step: no bias, no ReLU, and no derivative of
+ * the forward's ADC (dy is taken as it comes).
+ * Refused (RRAM_EINVAL before the device is touched): everything
+ * rram_ip_fwd_xbar refuses about a cfg, N < 1, ceil(N / C) * qmax >= 2^31,
+ * M * K >= 2^31, a negative split_k and a workspace below
+ * rram_ip_bwd_data_xbar_workspace(..., split_k) bytes (S * M * K * 4 for S > 1
+ * splits over N; split_k as above).  M == 0 or K == 0 is RRAM_OK with no
+ * launch.  Any 4-byte operand alignment; every split gives the same bits.
+ * rram_ip_bwd_data_xbar_kernel_ids (host only): xbar:pack<vec|scalar> (dy
+ * 16-byte aligned and N % 4 == 0), xbar:ip_t<vec|scalar>/sS (w 16-byte aligned
+ * and K % 4 == 0), and xbar:finish when S > 1. */
+int rram_ip_bwd_data_xbar(const float* dy, const float* w, float* dx, int M, int N, int K, const rram_xbar_cfg* cfg,
+                          int split_k, void* ws, size_t ws_bytes, rram_stream_t stream);
+size_t rram_ip_bwd_data_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
+int rram_ip_bwd_data_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int dy_align16, int w_align16,
+                                     int split_k, size_t ws_bytes, char* out, size_t cap);
+
 /* dw += ..., db += ... (nullable), dx = ... (nullable). */
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw,
                 float* db, float* dx, int M, int N, int K, int transpose,

@@ -33,6 +33,8 @@
 // converts every input bit plane on its own: see the comment above that kernel.
 // The bit-sliced-weight read-out (k_ip_xbar_ws) converts every
 // weight slice's column sum on its own, on int8 codes and the int32 MFMA.
+// The transposed read-out (k_ip_xbar_t) is the input gradient read
+// from the same array the other way, the weights staged transposed.
 // The kernels are built from the shared pieces below; which kernel uses which,
 // and why k_conv_xbar keeps some text of its own, is above k_conv_xbar.
 #include <algorithm>
@@ -356,6 +358,179 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   pipeline(smem, STAGE, tile_span(z, P), P.spt, gload, compute, lstore, adc);
 
   ip_store(S, P, P.split > 1 ? P.part + (int64_t)z * P.M * P.N : nullptr, m0, n0 + nw, lh);
+}
+
+// The transposed read-out: the input gradient of the same array,
+// dx[m][k] = read-out of dy[m][n] . W[n][k], the voltages on the columns and the
+// currents summed along the rows.  The reduction runs over the ROW index n of
+// W [N][K], cut into crossbar tiles of C columns; everything but the weight
+// operand is k_ip_xbar's: dy is packed by k_xbar_pack (the DAC there), the
+// accumulator sets, the ADC between the loops, the pipeline and ip_store with
+// the output columns k in N's place.  In the kernel's Plan, N is the output
+// count (the caller's K, the pitch of a weight row) and K the reduction length
+// (the caller's N).
+//
+// Weight operand.  A K-step needs the block W[32 n][128 k]: read along k (a
+// weight row's contiguous floats), read back by the MFMA lanes along n (8
+// consecutive n of one k).  WStageT transposes on the way: thread (kq, nq)
+// loads the four quads W[32 s + 4 nq + i][k0 + 4 kq .. + 3], i = 0 .. 3 (the
+// transpose of the 4 x 4 block is a renaming of its 16 registers) and stores
+// four quads, output column 4 kq + c, n-quad nq.
+//
+// Placement.  wquad_lds would take these stores 4-way conflicted: a store
+// instruction's rows 4 kq + c all have the parity of c, so its XOR swizzle
+// reaches 4 of the 16 16-byte bank units.  The transposed region therefore has
+// a placement and a reader of its own (tquad_lds, tfrag) and wquad_lds stays as
+// it is: rows of 32 fp32 + 16 B pad, 9 units, so unit (9 row + q) mod 16.
+// Reads: a ds_read_b128 lane group holds 16 rows distinct mod 16 at one q, 16
+// distinct units.  Writes: lane l of wave v is kq = (l & 3) | (l >> 4) << 2 |
+// (v & 1) << 4, nq = (l >> 2 & 3) | (v >> 1) << 2, so a group of 16 lanes
+// (consecutive, or the read groups) holds all four kq mod 4 against four nq
+// distinct mod 4: unit (4 kq + nq + 9 c) mod 16, all 16.  A wave's load
+// instruction still covers 4 weight rows x 256 contiguous bytes.
+constexpr int TRB = KS * 4 + 16;     // transposed weight row bytes per K-step: 32 n of one k + 16 B pad
+constexpr int STAGE_T = A_B + BN * TRB;
+static_assert(2 * STAGE_T <= 160 * 1024, "LDS");
+
+__device__ __forceinline__ int tquad_lds(int row, int q) { return row * TRB + (q << 4); }
+
+// wfrag for the transposed region: output column kw's n = 16 lh + 8 g + j
+__device__ __forceinline__ x6::Parts tfrag(const char* stage_b, int kw, int lh, int g) {
+  const float4* sb = reinterpret_cast<const float4*>(stage_b + tquad_lds(kw, 4 * lh + 2 * g));
+  float b[8];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const float4 q = sb[u];
+    b[4 * u] = q.x, b[4 * u + 1] = q.y, b[4 * u + 2] = q.z, b[4 * u + 3] = q.w;
+  }
+  x6::Parts p;
+  x6::split8_safe(b, p);
+  return p;
+}
+
+// One K-step of the weights, transposed through registers: the block of 32
+// reduction rows n x 128 output columns from column k0 of w (row pitch `pitch`
+// floats), zero for n at and past nred and for the columns at and past `cols`
+// from k0, stored to the transposed region at lds_off of a stage.
+//
+// The loads carry no branch: a quad outside the matrix reads the matrix's first
+// element(s) instead and is zeroed by select in store(), after the loads have
+// landed.  With the zeros as the other arm of a branch around each load, the
+// compiler resolved the transpose's renaming right behind the load, a wait for
+// the load inside load(): the four loads of a step in series, and before the
+// MFMAs they were to hide behind.
+template <bool VEC>
+struct WStageT {
+  const float* w;    // the matrix: always readable, the stand-in address
+  const float* src;  // W[0][k0 + 4 kq]: this thread's column quad
+  int64_t pitch;
+  int n4, cols, nred, lds;  // cols: valid columns from this thread's first
+  int ok;                   // bit i: row i of the loaded step lies inside the matrix (and cols > 0)
+  float4 r[4];
+  __device__ __forceinline__ WStageT(const float* w_, int k0, int cols_, int nred_, int pitch_, int lds_off, int tid)
+      : w(w_), pitch(pitch_), nred(nred_), ok(0) {
+    const int l = tid & 63, v = tid >> 6;
+    const int kq = (l & 3) | ((l >> 4) << 2) | ((v & 1) << 4), nq = ((l >> 2) & 3) | ((v >> 1) << 2);
+    n4 = 4 * nq;
+    cols = cols_ - 4 * kq;
+    src = w_ + k0 + 4 * kq;
+    lds = lds_off + tquad_lds(4 * kq, nq);
+  }
+  __device__ __forceinline__ void load(int s) {
+    ok = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n = s * KS + n4 + i;
+      const bool in = n < nred && cols > 0;
+      ok |= static_cast<int>(in) << i;
+      const float* p = in ? src + n * pitch : w;
+      if (VEC) {  // pitch % 4 == 0, w 16-byte aligned
+        r[i] = *reinterpret_cast<const float4*>(p);
+      } else {
+        r[i].x = *p;
+        r[i].y = *(in && cols > 1 ? p + 1 : w);
+        r[i].z = *(in && cols > 2 ? p + 2 : w);
+        r[i].w = *(in && cols > 3 ? p + 3 : w);
+      }
+    }
+  }
+  // element c of loaded row i, zero outside the matrix
+  __device__ __forceinline__ float at(int i, float v, int c) const {
+    return ((ok >> i) & 1) && (VEC || cols > c) ? v : 0.0f;
+  }
+  __device__ __forceinline__ void store(char* st) const {
+    float4* d = reinterpret_cast<float4*>(st + lds);
+    d[0 * (TRB / 16)] = make_float4(at(0, r[0].x, 0), at(1, r[1].x, 0), at(2, r[2].x, 0), at(3, r[3].x, 0));
+    d[1 * (TRB / 16)] = make_float4(at(0, r[0].y, 1), at(1, r[1].y, 1), at(2, r[2].y, 1), at(3, r[3].y, 1));
+    d[2 * (TRB / 16)] = make_float4(at(0, r[0].z, 2), at(1, r[1].z, 2), at(2, r[2].z, 2), at(3, r[3].z, 2));
+    d[3 * (TRB / 16)] = make_float4(at(0, r[0].w, 3), at(1, r[1].w, 3), at(2, r[2].w, 3), at(3, r[3].w, 3));
+  }
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_ip_xbar_t(Plan P) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_T];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const int id = xcd_tile_id(blockIdx.x, gridDim.x);
+  const int tm = __builtin_amdgcn_readfirstlane(id % P.tiles_m);
+  const int tn = __builtin_amdgcn_readfirstlane((id / P.tiles_m) % P.tiles_n);
+  const int z = __builtin_amdgcn_readfirstlane(id / (P.tiles_m * P.tiles_n));
+  const int m0 = tm * BM, n0 = tn * BN;  // n0: the tile's first output column
+
+  // this thread's pieces of a K-step: the packed dy as in k_ip_xbar (why the
+  // copy is written in each kernel: there) and the transposing stager's quads
+  const char* asrc = P.apack + (int64_t)tm * P.ksteps * A_B + tid * 16;
+  uint4 ra[A_LD];
+  WStageT<VEC> ws(P.w, n0, P.N - n0, P.K, P.N, A_B, tid);
+  auto gload = [&](int s) {
+    const char* a = asrc + (int64_t)s * A_B;
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i)
+      if (tid + 256 * i < A_U) ra[i] = *reinterpret_cast<const uint4*>(a + 4096 * i);
+    ws.load(s);
+  };
+  auto lstore = [&](char* st) {
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i)
+      if (tid + 256 * i < A_U) *reinterpret_cast<uint4*>(st + tid * 16 + 4096 * i) = ra[i];
+    ws.store(st);
+  };
+
+  floatx16 acc[MI];   // the current crossbar tile's partial sums
+  int32_t S[MI][16];  // the digital sum of the ADC codes
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[i][r] = 0.0f;
+      S[i][r] = 0;
+    }
+
+  const int kw = 32 * wave + lr;  // this lane's output column inside the tile
+  auto compute = [&](const char* st) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const x6::Parts bp = tfrag(st + A_B, kw, lh, g);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+        acc[i] = x6::mfma6(term_parts(st + (i * 32 + lr) * RLB + (g * 2 + lh) * 48), bp, acc[i]);
+    }
+  };
+  auto adc = [&]() {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        S[i][r] += adc_code(acc[i][r], P.inv_step, P.qmax);
+        acc[i][r] = 0.0f;
+      }
+  };
+  pipeline(smem, STAGE_T, tile_span(z, P), P.spt, gload, compute, lstore, adc);
+
+  ip_store(S, P, P.split > 1 ? P.part + (int64_t)z * P.M * P.N : nullptr, m0, n0 + kw, lh);
 }
 
 // The bit-serial read-out: the DAC code c of every activation is
@@ -1218,6 +1393,71 @@ int ip_fwd(bool serial, const float* x, const float* w, const float* bias, float
   return launch_finish(serial ? "ip_fwd_xbar_bs finish" : "ip_fwd_xbar finish", P, slabs, M, N, 1, s);
 }
 
+// The transposed read-out's checks (host only): cfg->rows is the number of array
+// columns C one read sums over, N the reduction length, K the output count.
+int bwd_check(int M, int N, int K, const rram_xbar_cfg* c, int split_k) {
+  const char* who = "ip_bwd_data_xbar";
+  RRAM_REQUIRE(M >= 0 && N >= 1 && K >= 0, "%s: bad shape %d x %d x %d", who, M, N, K);
+  const int rc = check_cfg(c, who);
+  if (rc) return rc;
+  RRAM_REQUIRE(split_k >= 0, "%s: negative split_k", who);
+  const int64_t ntiles = (N + c->rows - 1) / c->rows, qmax = (1 << (c->adc_bits - 1)) - 1;
+  RRAM_REQUIRE(ntiles * qmax < (1ll << 31), "%s: %lld tiles x qmax %lld overflows int32", who, (long long)ntiles,
+               (long long)qmax);
+  RRAM_REQUIRE((int64_t)M * K < (1ll << 31), "%s: more than 2^31 outputs", who);
+  return RRAM_OK;
+}
+
+// the kernel's Plan: N is the output count (the caller's K), K the reduction length (the caller's N)
+void make_bwd_plan(int M, int N, int K, const rram_xbar_cfg& c, int split_k, size_t ws_bytes, Plan& P) {
+  P = Plan{};
+  P.M = M, P.N = K, P.K = N;
+  P.tiles_m = (M + BM - 1) / BM;
+  P.tiles_n = (K + BN - 1) / BN;
+  plan_core(P, N, c, (int64_t)P.tiles_m * P.tiles_n, (size_t)M * K * sizeof(int32_t), split_k, ws_bytes);
+}
+
+int bwd_data(const float* dy, const float* w, float* dx, int M, int N, int K, const rram_xbar_cfg* cfg, int split_k,
+             void* ws, size_t ws_bytes, rram_stream_t st) {
+  const char* who = "ip_bwd_data_xbar";
+  const int rc0 = bwd_check(M, N, K, cfg, split_k);
+  if (rc0) return rc0;
+  if (M == 0 || K == 0) return RRAM_OK;
+  RRAM_REQUIRE(dy && w && dx, "%s: NULL", who);
+  Plan P;
+  make_bwd_plan(M, N, K, *cfg, split_k, ws != nullptr ? ws_bytes : 0, P);
+  const int rcw = require_ws(who, ws, ws_bytes, part_bytes(P.split, (int64_t)M * K), P.split, 0);
+  if (rcw) return rcw;
+  RRAM_REQUIRE((int64_t)P.tiles_m * P.tiles_n * P.split < (1ll << 31), "%s: grid too large", who);
+  hipStream_t s = as_stream(st);
+  const bool yv = al16(dy, N), wv = al16(w, K);
+
+  if (!plan_note("xbar:pack<%s>", yv ? "vec" : "scalar")) {  // dy through the forward's pack, N as its K
+    const Steps dac = steps_of(*cfg);
+    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * A_B;
+    char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
+    RRAM_REQUIRE(pb != nullptr, "%s: packed-gradient buffer allocation failed", who);
+    P.apack = pb;
+    const int64_t units = (int64_t)P.tiles_m * BM * P.ksteps * 4;
+    by_vec(yv, [&](auto V) {
+      hipLaunchKernelGGL(k_xbar_pack<decltype(V)::value>, dim3(stream_blocks(units)), dim3(256), 0, s, dy, M, N, pb,
+                         P.ksteps, units, dac.dac_xs, dac.dac_qmax);
+    });
+    const int rc = launch_status("ip_bwd_data_xbar pack");
+    if (rc) return rc;
+  }
+  P.w = w;
+  P.y = dx;
+  P.part = P.split > 1 ? static_cast<int32_t*>(ws) : nullptr;
+  if (!plan_note("xbar:ip_t<%s>/s%d", wv ? "vec" : "scalar", P.split)) {
+    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * P.split));
+    by_vec(wv, [&](auto V) { hipLaunchKernelGGL(k_ip_xbar_t<decltype(V)::value>, grid, dim3(256), 0, s, P); });
+    const int rc = launch_status(who);
+    if (rc) return rc;
+  }
+  return launch_finish("ip_bwd_data_xbar finish", P, P.split, M, K, 1, s);
+}
+
 // The bit-sliced-weight read-out's checks (host only).  Both operands must fit
 // int8, and S (so every partial slab too) int32: |S| <= ntiles * qmax * sum_s 2^(s cb).
 constexpr int WS_PC = 4;  // slices per chunk: the one k_ip_xbar_ws instantiation
@@ -1389,6 +1629,27 @@ int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg
   rram::PlanScope sc;
   const int rc = rram_ip_fwd_xbar_ws(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
                                      slices, 0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
+  return rc ? rc : rram::copy_text(sc.text, out, cap);
+}
+
+size_t rram_ip_bwd_data_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k) {
+  if (rram::xb::bwd_check(M, N, K, cfg, split_k) != RRAM_OK || M == 0 || K == 0) return 0;
+  rram::xb::Plan P;
+  rram::xb::make_bwd_plan(M, N, K, *cfg, split_k, ~static_cast<size_t>(0), P);
+  return rram::xb::part_bytes(P.split, (int64_t)M * K);
+}
+
+int rram_ip_bwd_data_xbar(const float* dy, const float* w, float* dx, int M, int N, int K, const rram_xbar_cfg* cfg,
+                          int split_k, void* ws, size_t ws_bytes, rram_stream_t st) {
+  return rram::xb::bwd_data(dy, w, dx, M, N, K, cfg, split_k, ws, ws_bytes, st);
+}
+
+int rram_ip_bwd_data_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int dy_align16, int w_align16,
+                                     int split_k, size_t ws_bytes, char* out, size_t cap) {
+  using rram::xb::fake_ptr;
+  rram::PlanScope sc;
+  const int rc = rram_ip_bwd_data_xbar(fake_ptr(dy_align16), fake_ptr(w_align16), fake_ptr(1), M, N, K, cfg, split_k,
+                                       ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

@@ -147,13 +147,42 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
 // weight_range } } or, for a layer with a crossbar and no weight_slices of its
 // own, the Net option `crossbar_slices` ("weight_bits,cell_bits,weight_range",
 // handed down as rram_crossbar_slices).
+// bwd->rows != 0: the transposed read-out of the input gradient
+// (rram_ip_bwd_data_xbar) is asked for, by crossbar_param { backward { cols
+// adc_bits adc_range [dac_bits dac_range] } } or, for a layer with a crossbar
+// and no backward of its own, the Net option `crossbar_backward`
+// ("cols,adc_bits,adc_range[,dac_bits,dac_range]", handed down as
+// rram_crossbar_backward); cols goes to rram_xbar_cfg::rows.
 static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c, bool* bit_serial,
-                          rram_xbar_slices* sl) {
+                          rram_xbar_slices* sl, rram_xbar_cfg* bwd) {
   const Msg* xp = lp.sub("crossbar_param");
   *bit_serial = false;
   *sl = rram_xbar_slices{0, 0, 0.0f};
+  *bwd = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
   if (xp == nullptr && !lp.has("rram_crossbar")) return false;
   *c = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
+  const Msg* bp = xp != nullptr ? xp->sub("backward") : nullptr;
+  if (bp != nullptr) {
+    bwd->rows = static_cast<int32_t>(bp->integer("cols", 0));
+    bwd->adc_bits = static_cast<int32_t>(bp->integer("adc_bits", 0));
+    bwd->adc_range = static_cast<float>(bp->num("adc_range", 0.0));
+    bwd->dac_bits = static_cast<int32_t>(bp->integer("dac_bits", 0));
+    bwd->dac_range = static_cast<float>(bp->num("dac_range", 1.0));
+    CAFFE_CHECK(bwd->rows != 0, name << ": backward wants cols");
+  } else if (lp.has("rram_crossbar_backward")) {
+    std::vector<double> v;
+    std::stringstream ss(lp.str("rram_crossbar_backward"));
+    std::string t;
+    try {
+      while (std::getline(ss, t, ',')) v.push_back(std::stod(t));
+    } catch (const std::exception&) {
+      v.clear();
+    }
+    CAFFE_CHECK((v.size() == 3 || v.size() == 5) && v[0] != 0.0,
+                name << ": option crossbar_backward wants cols,adc_bits,adc_range[,dac_bits,dac_range]");
+    *bwd = rram_xbar_cfg{static_cast<int32_t>(v[0]), static_cast<int32_t>(v[1]), static_cast<float>(v[2]), 0, 1.0f};
+    if (v.size() == 5) bwd->dac_bits = static_cast<int32_t>(v[3]), bwd->dac_range = static_cast<float>(v[4]);
+  }
   const Msg* sp = xp != nullptr ? xp->sub("weight_slices") : nullptr;
   if (sp != nullptr) {
     sl->weight_bits = static_cast<int32_t>(sp->integer("weight_bits", 0));
@@ -220,9 +249,11 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom
   bias_term_ = cp.boolean("bias_term", true);
   bool bit_serial = false;
   rram_xbar_slices slices{};
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial, &slices);
+  rram_xbar_cfg backward{};
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial, &slices, &backward);
   CAFFE_CHECK(!bit_serial, this->name() << ": bit_serial is not served for Convolution");
   CAFFE_CHECK(slices.weight_bits == 0, this->name() << ": weight_slices is not served for Convolution");
+  CAFFE_CHECK(backward.rows == 0, this->name() << ": backward is not served for Convolution");
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan
     // query for one image (before any blob is allocated: no device is touched)
@@ -455,7 +486,7 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
   axis_ = static_cast<int>(ip.integer("axis", 1));
   if (axis_ < 0) axis_ += bottom[0]->num_axes();
   K_ = static_cast<int>(bottom[0]->count(axis_));
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_, &slices_);
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_, &slices_, &xbar_bwd_);
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan query
     // (the bit-serial and bit-sliced ones with the workspace their chunks and planes need;
@@ -472,6 +503,8 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
                                                                sizeof id)
                               : rram_ip_fwd_xbar_kernel_ids(1, N_, K_, &xbar_, 1, 1, 0, 0, id, sizeof id);
     CAFFE_CHECK(rc > 0, this->name() << ": crossbar_param: " << rram_last_error());
+    CAFFE_CHECK(!xbar_bwd() || rram_ip_bwd_data_xbar_kernel_ids(1, N_, K_, &xbar_bwd_, 1, 1, 0, 0, id, sizeof id) > 0,
+                this->name() << ": crossbar_param backward: " << rram_last_error());
   }
   this->blobs_.clear();
   this->blobs_.push_back(std::make_shared<Blob<Dtype>>(
@@ -569,11 +602,17 @@ void InnerProductLayer<Dtype>::Backward_gpu(const std::vector<Blob<Dtype>*>& top
                                             const std::vector<bool>& pd,
                                             const std::vector<Blob<Dtype>*>& bottom) {
   CAFFE_CHECK(groups_ == 1, this->name() << ": backward through map groups is not supported (inference only)");
+  const bool dx = pd.size() && pd[0];
   RRAM_CALL(rram_ip_bwd(bottom[0]->gpu_data(), this->blobs_[0]->gpu_data(), top[0]->gpu_diff(),
                         this->param_propagate_down(0) ? this->blobs_[0]->mutable_gpu_diff() : nullptr,
                         (bias_term_ && this->param_propagate_down(1)) ? this->blobs_[1]->mutable_gpu_diff() : nullptr,
-                        (pd.size() && pd[0]) ? bottom[0]->mutable_gpu_diff() : nullptr, M_, N_, K_,
+                        (dx && !xbar_bwd()) ? bottom[0]->mutable_gpu_diff() : nullptr, M_, N_, K_,
                         transpose_ ? 1 : 0, Caffe::stream()));
+  if (dx && xbar_bwd()) {  // the input gradient read from the array the other way, the same weights
+    void* ws = Caffe::workspace(ws_request());
+    RRAM_CALL(rram_ip_bwd_data_xbar(top[0]->gpu_diff(), this->blobs_[0]->gpu_data(), bottom[0]->mutable_gpu_diff(), M_,
+                                    N_, K_, &xbar_bwd_, 0, ws, Caffe::workspace_size(), Caffe::stream()));
+  }
 }
 
 // ------------------------------------------------------------------ ReLU

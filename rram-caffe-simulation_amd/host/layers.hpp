@@ -116,10 +116,11 @@ class InnerProductLayer : public Layer<Dtype> {
   int M_ = 0, N_ = 0, K_ = 0, axis_ = 1;
   bool bias_term_ = true, transpose_ = false;
   // split-K partials need up to 16 x M x N floats (<= 256 MB); the crossbar
-  // forward its planner's int32 partials
+  // forward its planner's int32 partials, the transposed read-out its own
   size_t ws_request() const {
-    const size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
+    size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
     if (!xbar_on_) return f32;
+    if (xbar_bwd()) f32 = std::max(f32, rram_ip_bwd_data_xbar_workspace(M_, N_, K_, &xbar_bwd_, 0));
     if (xbar_ws()) return std::max(f32, rram_ip_fwd_xbar_ws_workspace(M_ / groups_, N_, K_, &xbar_, &slices_, 0));
     const auto need = xbar_bs_ ? rram_ip_fwd_xbar_bs_workspace : rram_ip_fwd_xbar_workspace;
     return std::max(f32, need(M_ / groups_, N_, K_, &xbar_, 0));
@@ -133,6 +134,11 @@ class InnerProductLayer : public Layer<Dtype> {
   // read-out rram_ip_fwd_xbar_ws, one conversion per weight slice (weight_bits 0: not asked for)
   rram_xbar_slices slices_{};
   bool xbar_ws() const { return slices_.weight_bits != 0; }
+  // backward (or the Net option `crossbar_backward`): the input gradient is the
+  // transposed read-out rram_ip_bwd_data_xbar with this configuration, rows = the
+  // array columns of one read (rows 0: not asked for, the straight-through rram_ip_bwd)
+  rram_xbar_cfg xbar_bwd_{};
+  bool xbar_bwd() const { return xbar_bwd_.rows != 0; }
   uint64_t in_rows_key_ = 0;  // the packed-row companion this layer reads (Reshape; 0: none)
   // set_map_groups: the batch rows are groups_ groups of M_ / groups_ rows,
   // group g reading copy g of a faulted blob (nullptr: the layer's own blob)

@@ -198,6 +198,10 @@ Net<Dtype>::Net(const Msg& in_param, Phase phase, const Msg& options) : phase_(p
     // (read_crossbar; a Convolution layer refuses it)
     if ((type == "InnerProduct" || type == "Convolution") && options.has("crossbar_slices"))
       lp.set("rram_crossbar_slices", options.str("crossbar_slices"));
+    // option crossbar_backward: every such layer that has a crossbar and no backward of its own
+    // (read_crossbar; a Convolution layer refuses it)
+    if ((type == "InnerProduct" || type == "Convolution") && options.has("crossbar_backward"))
+      lp.set("rram_crossbar_backward", options.str("crossbar_backward"));
     auto layer = LayerRegistry<Dtype>::CreateLayer(lp);
     layer->layer_id = static_cast<uint32_t>(lid);
     const std::string lname = lp.str("name");

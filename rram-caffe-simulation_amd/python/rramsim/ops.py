@@ -501,6 +501,23 @@ def ip_fwd_xbar_ws_kernel_ids(M, N, K_, cfg, slices, x_align16=True, w_align16=T
                      int(w_align16), split_k, int(ws_bytes))
 
 
+def ip_bwd_data_xbar(dy, w, dx, M, N, K_, cfg, split_k=0, workspace=None):
+    """rram_ip_bwd_data_xbar: dx = the ADC read-out of dy . w, the array read the other way, from tiles of
+    cfg.rows array columns over N (cfg: this read's own; split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_bwd_data_xbar(_p(dy), _p(w), _p(dx), M, N, K_, C.byref(cfg), split_k, _p(workspace), wsb,
+                                         _stream()), "ip_bwd_data_xbar")
+
+
+def ip_bwd_data_xbar_workspace(M, N, K_, cfg, split_k=0):
+    return _lib().rram_ip_bwd_data_xbar_workspace(M, N, K_, C.byref(cfg), split_k)
+
+
+def ip_bwd_data_xbar_kernel_ids(M, N, K_, cfg, dy_align16=True, w_align16=True, split_k=0, ws_bytes=0):
+    return _id_lines(_lib().rram_ip_bwd_data_xbar_kernel_ids, M, N, K_, C.byref(cfg), int(dy_align16),
+                     int(w_align16), split_k, int(ws_bytes))
+
+
 def conv_fwd_xbar(d, x, w, bias, y, cfg, relu=False, split_k=0, workspace=None):
     """rram_conv2d_fwd_xbar: y = the ADC read-out of conv(x, w) from crossbars of cfg.rows rows of the
     unrolled kernel (d: a conv_desc; split_k 0: planner)."""

@@ -6,11 +6,13 @@ conv2 / conv8 and a GoogLeNet 1x1, or with --serial the bit-serial
 rram_ip_fwd_xbar_bs beside rram_ip_fwd_xbar with the same DAC (dac_bits 4 and 8)
 on the InnerProduct shapes, or with --sliced the bit-sliced-weight
 rram_ip_fwd_xbar_ws (weight_bits 8, cell_bits 2 and 1) beside rram_ip_fwd_xbar
-with the same 8-bit DAC.  Call times from device events (every launch
-of the call included), the two alternated in one process, the median and range
-of REPS windows of ITERS calls each.
+with the same 8-bit DAC, or with --backward the transposed read-out
+rram_ip_bwd_data_xbar beside rram_ip_bwd with only dx wanted and beside
+rram_ip_fwd_xbar on the mirrored shape.  Call times from device events (every
+launch of the call included), the two alternated in one process, the median and
+range of REPS windows of ITERS calls each.
 
-    python scripts/xbar_bench.py [--conv | --serial | --sliced] [out.txt]
+    python scripts/xbar_bench.py [--conv | --serial | --sliced | --backward] [out.txt]
 
 --sliced --shape=fc6 --cells=2 keeps one shape and one cell width, so that a
 kernel trace of the run (per-kernel totals) gives the weight pack's share of
@@ -150,12 +152,50 @@ def conv_rows():
     return lines
 
 
+def backward_rows():
+    """rram_ip_bwd_data_xbar (dx from dy [M][N] and w [N][K], tiles of C columns over N) beside (a) rram_ip_bwd
+    with only dx wanted and (b) rram_ip_fwd_xbar on the mirrored shape (M, N' = K, K' = N): the same MFMAs,
+    the weights staged as they lie.  The three alternated window by window."""
+    lines = ["shape  M x N x K  C B | transposed xbar us (min..max) ids | (a) plain dx us (min..max) ids | "
+             "(b) mirrored forward xbar us (min..max) ids | ratio to (a) | ratio to (b)"]
+    for name, M, N, K, C, B in SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(1)
+        dy = torch.randn(M, N, device="cuda", generator=g)
+        w = torch.randn(N, K, device="cuda", generator=g) * N ** -0.5
+        wm = w.t().contiguous()                                      # [K][N]: (b)'s weight rows run along N
+        x, dx = torch.randn(M, K, device="cuda", generator=g), torch.empty(M, K, device="cuda")
+        cfg = ops.xbar_cfg(C, B, 4.0)
+        wst = torch.empty(max(1, ops.ip_bwd_data_xbar_workspace(M, N, K, cfg)), dtype=torch.uint8, device="cuda")
+        wsf = torch.empty(max(1, ops.ip_fwd_xbar_workspace(M, K, N, cfg)), dtype=torch.uint8, device="cuda")
+        fns = [lambda: ops.ip_bwd_data_xbar(dy, w, dx, M, N, K, cfg, workspace=wst),
+               lambda: ops.ip_bwd(x, w, dy, None, None, dx, M, N, K),
+               lambda: ops.ip_fwd_xbar(dy, wm, None, dx, M, K, N, cfg, workspace=wsf)]
+        ids = [ops.ip_bwd_data_xbar_kernel_ids(M, N, K, cfg, ws_bytes=wst.numel()),
+               ops.ip_bwd_kernel_ids(M, N, K, dw=False, db=False),
+               ops.ip_fwd_xbar_kernel_ids(M, K, N, cfg, ws_bytes=wsf.numel())]
+        for f in fns:
+            for _ in range(5):
+                f()
+        torch.cuda.synchronize()
+        t = [[], [], []]
+        for _ in range(REPS):
+            for i, f in enumerate(fns):
+                t[i].append(window(f))
+        med = [sorted(v)[REPS // 2] for v in t]
+        cols = [f"{med[i]:.1f} ({min(t[i]):.1f}..{max(t[i]):.1f}) {','.join(ids[i])}" for i in range(3)]
+        lines.append(f"{name}  {M} x {N} x {K}  {C} {B} | " + " | ".join(cols) +
+                     f" | {med[0] / med[1]:.2f} | {med[0] / med[2]:.2f}")
+    return lines
+
+
 def main():
     assert torch.cuda.is_available(), "needs a GPU"
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     args = [a for a in sys.argv[1:] if a not in flags]
     opt = dict(f[2:].split("=", 1) for f in flags if "=" in f)
     rows = conv_rows if "--conv" in flags else serial_rows if "--serial" in flags else ip_rows
+    if "--backward" in flags:
+        rows = backward_rows
     if "--sliced" in flags:
         rows = lambda: sliced_rows(opt.get("shape"), int(opt.get("cells", 0)))  # noqa: E731
     text = "\n".join(rows()) + "\n"
