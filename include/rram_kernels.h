@@ -776,6 +776,47 @@ size_t rram_ip_fwd_xbar_ws_workspace(int M, int N, int K, const rram_xbar_cfg* c
                                      int split_k);
 int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
                                    int x_align16, int w_align16, int split_k, size_t ws_bytes, char* out, size_t cap);
+/* The digit-serial read-out of the bit-sliced arrays (no reference
+ * counterpart): the input code is streamed digit_bits bits per
+ * cycle through a narrow DAC against the weight slices of
+ * rram_ip_fwd_xbar_ws, the ADC converts the column sum of every (input digit,
+ * weight slice) pair of every tile on its own, and a shift-and-add combines
+ * the codes.  cfg, slices, every scalar (cmax, dmax, qmax, xs, ws, kf,
+ * out_scale), the codes c and d and the slices d_s are rram_ip_fwd_xbar_ws's.
+ * With db = digit_bits and Nd = ceil((dac_bits - 1) / db):
+ *   c_j = sign(c) * ((|c| >> j * db) & (2^db - 1)), j = 0 .. Nd-1
+ *         (sign-magnitude; the top digit may be narrower),
+ *   p_{t,j,s} = sum over the tile's rows of c_j * d_s (int32, exact),
+ *   q_{t,j,s} = clamp(rint(float(p_{t,j,s}) * kf), +-qmax)   (half to even),
+ *   S = sum_t sum_j sum_s q_{t,j,s} << (j * db + s * cell_bits) (int32),
+ *   y = float(S) * out_scale + bias, ReLU.
+ * adc_range is the full scale of ONE (digit, slice) pair's column sum in x * w
+ * units, the digit counted in units of xs and the slice in units of ws
+ * (neither scaled by its position).  digit_bits = dac_bits - 1 is one digit:
+ * the bits of rram_ip_fwd_xbar_ws.
+ * Refused (RRAM_EINVAL before the device is touched): everything
+ * rram_ip_fwd_xbar_ws refuses, digit_bits outside [1, dac_bits - 1], and
+ * ceil(K / rows) * qmax * sum_j 2^(j * db) * sum_s 2^(s * cell_bits) >= 2^31.
+ * M == 0 or N == 0 is RRAM_OK with no launch.
+ * The workspace (16-byte aligned) holds the slice planes as for
+ * rram_ip_fwd_xbar_ws.  The pairs are cut into chunks of up to PD digits x 4
+ * slices (PD = 3, or 2 where that takes no more chunks: Nd = 1, 2, 4),
+ * C = ceil(Nd / PD) * ceil(Ns / 4) of them, a further factor of the grid
+ * beside the S splits over K: with S * C > 1 the int32 slabs add
+ * S * C * M * N * 4 bytes.  rram_ip_fwd_xbar_ss_workspace gives the sum
+ * (split_k = 0: the most the planner would use); less is RRAM_EINVAL.  S is an
+ * integer: every split and every chunking give the same bits.
+ * rram_ip_fwd_xbar_ss_kernel_ids (host only): xbar:pack_sm8<vec|scalar>,
+ * xbar:pack_wslices<vec|scalar>, xbar:ip_ss<dPD;pPS>/sS/cC (PD digits x PS = 4
+ * slices per chunk), and xbar:finish when S * C > 1. */
+int rram_ip_fwd_xbar_ss(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices, int digit_bits,
+                        int relu, int split_k, void* ws, size_t ws_bytes, rram_stream_t stream);
+size_t rram_ip_fwd_xbar_ss_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                     int digit_bits, int split_k);
+int rram_ip_fwd_xbar_ss_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                   int digit_bits, int x_align16, int w_align16, int split_k, size_t ws_bytes,
+                                   char* out, size_t cap);
 /* The crossbar-tiled Convolution forward (no reference counterpart; DESIGN
  * §7.5): the array of group g holds the unrolled kernel, rows
  * k = (ci * kernel_h + i) * kernel_w + j (Caffe's im2col / weight-blob order),

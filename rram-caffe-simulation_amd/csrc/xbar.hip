@@ -33,6 +33,8 @@
 // converts every input bit plane on its own: see the comment above that kernel.
 // The bit-sliced-weight read-out (k_ip_xbar_ws) converts every
 // weight slice's column sum on its own, on int8 codes and the int32 MFMA.
+// Its digit-serial form (k_ip_xbar_ss) streams the input code a few
+// bits per cycle against those slices, one conversion per (digit, slice) pair.
 // The transposed read-out (k_ip_xbar_t) is the input gradient read
 // from the same array the other way, the weights staged transposed.
 // The kernels are built from the shared pieces below; which kernel uses which,
@@ -892,6 +894,170 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
   ip_store(S, P, P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr, m0, n0 + nw, lh);
 }
 
+// The digit-serial read-out of the bit-sliced array: the input
+// code c is streamed db bits per cycle, digit j holding c_j = sign(c) *
+// ((|c| >> j db) & (2^db - 1)), against the weight slices d_s of §7.7; the ADC
+// converts the column sum of every (digit, slice) pair of every crossbar tile
+// on its own and a shift-and-add combines the codes:
+//   S[m][n] = sum_t sum_j sum_s q_{t,j,s}[m][n] << (j db + s cb) (int32).
+// Both operands of a pair are int8, so its column sum is one exact int32 MFMA
+// per K-step, Nd Ns of them per product.
+//
+// Activations.  k_xbar_pack_sm8 writes the sign-magnitude byte of every code
+// (bit 7 the sign, bits 0..6 |c|) in k_xbar_pack_i8's LDS image on 32-row
+// tiles.  No digit exists in memory: a lane forms digit j of its 16 codes in
+// registers from the one 16-byte fragment, four bytes to a word.  With the
+// sign bits s (0x80 per negative byte) taken off, d = (mag >> j db) & mask has
+// at most 7 bits per byte (the mask of the top digit stops at bit 6, so that no
+// bit of the next byte comes in), and the two's-complement byte of -d is
+//   ((d ^ 0x7F) + 1) ^ 0x80:  127 - d + 1 = 128 - d in [1, 128] never carries
+// out of its byte, and flipping bit 7 makes it 256 - d mod 256, 0 for d = 0
+// (~d + 1 carries into the next byte exactly there).  Under the byte's sign:
+//   a = ((d ^ m7) + s1) ^ s,  s1 = s >> 7, m7 = s - s1 (0x7F per negative byte),
+// three operations per word and digit after the shift and the mask.
+//
+// Work split.  A workgroup (4 waves) owns 32 rows x 128 columns for a range of
+// whole crossbar tiles and one chunk of up to PD digits x PS slices; wave w
+// owns columns 32 w .. 32 w + 31: one 32 x 32 block with PD PS int32 sets (one
+// per pair) and the int32 set S.  Per K-step a lane reads one activation
+// fragment and PS slice fragments and issues PD PS MFMAs: one digit fragment
+// serves every slice, one slice fragment every digit.  The ADC, the clearing
+// through the matrix pipe, the stage copies and the pipeline are
+// k_ip_xbar_ws's.  Digit chunks and slice chunks are grid factors combined
+// like K splits: slabs [slice chunk][digit chunk][split][M][N], k_xbar_finish.
+struct Ssl {
+  static constexpr int BM = 32;
+  static constexpr int A_B = BM * QRB;  // code bytes per K-step and row tile
+  static constexpr int A_U = A_B / 16;  // ... in 16-byte units, below the 256 threads
+  static_assert(A_U <= 256, "one unit per thread");
+};
+
+struct SsPlan : WsPlan {  // WsPlan::chunks = cd * cs
+  int nd, db;             // digits of an input code, bits of a digit
+  int pd;                 // digits per chunk: which instantiation (host only)
+  int cd, cs;             // digit chunks ceil(nd / PD), slice chunks ceil(ns / PS)
+};
+
+// x [M][K] fp32 -> sign-magnitude int8 DAC codes (bit 7: c < 0, bits 0..6: |c|,
+// c = clamp(rint(x / xs), +-cmax)) in the K-step slabs k_ip_xbar_ss copies to
+// LDS (zero past M and K, zero pad).  One thread per unit: 8 activations in, 8
+// bytes out.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_xbar_pack_sm8(const float* __restrict__ x, int M, int K,
+                                                       char* __restrict__ out, int ksteps, int64_t units, float xs,
+                                                       float cmax) {
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    float v[8];
+    const PackUnit U = pack_unit<VEC>(u, x, M, K, ksteps, out, Ssl::BM, QRB, v);
+    uint32_t cw[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float c = __builtin_amdgcn_fmed3f(__builtin_rintf(v[j] / xs), -cmax, cmax);
+      cw[j >> 2] |= (static_cast<uint32_t>(__builtin_fabsf(c)) | (c < 0.0f ? 0x80u : 0u)) << (8 * (j & 3));
+    }
+    *reinterpret_cast<uint2*>(U.row + U.h * 16 + U.g * 8) = make_uint2(cw[0], cw[1]);
+    if (U.g == 1 && U.h == 1) *reinterpret_cast<uint4*>(U.row + 32) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+template <int PD, int PS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_ip_xbar_ss(SsPlan P) {
+  typedef Ssl T;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+  typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
+  constexpr int STAGE_B = T::A_B + PS * Wsl::P_B;
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_B];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const int id = xcd_tile_id(blockIdx.x, gridDim.x);
+  const int tm = __builtin_amdgcn_readfirstlane(id % P.tiles_m);
+  const int tn = __builtin_amdgcn_readfirstlane((id / P.tiles_m) % P.tiles_n);
+  const int zc = __builtin_amdgcn_readfirstlane(id / (P.tiles_m * P.tiles_n));  // chunk * split + z: the slab
+  const int z = zc % P.split, ch = zc / P.split;
+  const int jd0 = (ch % P.cd) * PD, js0 = (ch / P.cd) * PS;  // the chunk's first digit and slice
+  const int npd = min(PD, P.nd - jd0), nps = min(PS, P.ns - js0);  // ... and how many it has
+  const int m0 = tm * T::BM, n0 = tn * BN;
+
+  // this thread's pieces of a K-step, copied as they lie: one 16-byte unit of the
+  // codes (the first A_U threads) and one of each of the chunk's nps slice planes
+  const char* asrc = P.apack + (int64_t)tm * P.ksteps * T::A_B + tid * 16;
+  const char* bsrc = P.wplanes + ((int64_t)tn * P.ksteps * P.ns + js0) * Wsl::P_B + tid * 16;
+  uint4 ra, rb[PS];
+  auto gload = [&](int s) {
+    if (tid < T::A_U) ra = *reinterpret_cast<const uint4*>(asrc + (int64_t)s * T::A_B);
+#pragma unroll
+    for (int j = 0; j < PS; ++j)
+      if (j < nps) rb[j] = *reinterpret_cast<const uint4*>(bsrc + ((int64_t)s * P.ns + j) * Wsl::P_B);
+  };
+  auto lstore = [&](char* st) {
+    if (tid < T::A_U) *reinterpret_cast<uint4*>(st + tid * 16) = ra;
+#pragma unroll
+    for (int j = 0; j < PS; ++j)
+      if (j < nps) *reinterpret_cast<uint4*>(st + T::A_B + j * Wsl::P_B + tid * 16) = rb[j];
+  };
+
+  // a cleared set comes out of the matrix pipe, as in k_ip_xbar_bs and k_ip_xbar_ws
+  auto zero_set = [&]() {
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(i32x4{0, 0, 0, 0}, i32x4{0, 0, 0, 0}, i32x16{}, 0, 0, 0);
+  };
+  i32x16 acc[PD][PS];  // the current crossbar tile's column sums, one set per (digit, slice) pair
+  int32_t S[1][16];    // the shift-and-add of the ADC codes
+#pragma unroll
+  for (int jd = 0; jd < PD; ++jd)
+#pragma unroll
+    for (int js = 0; js < PS; ++js) acc[jd][js] = zero_set();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) S[0][r] = 0;
+
+  // digit jd of the chunk: its shift and its per-byte mask, which stops at bit 6
+  uint32_t dsh[PD], dmk[PD];
+#pragma unroll
+  for (int jd = 0; jd < PD; ++jd) {
+    dsh[jd] = static_cast<uint32_t>(min((jd0 + jd) * P.db, 6));
+    dmk[jd] = ((1u << min(P.db, 7 - static_cast<int>(dsh[jd]))) - 1u) * 0x01010101u;
+  }
+
+  const int nw = 32 * wave + lr;  // this lane's weight row (output column) inside the tile
+  const int aoff = lr * QRB + lh * 16, boff = T::A_B + wslice_lds(nw, lh);
+  auto compute = [&](const char* st) {
+    const u32x4 cw = *reinterpret_cast<const u32x4*>(st + aoff);
+    const u32x4 sg = cw & 0x80808080u, s1 = sg >> 7u, m7 = sg - s1, mag = cw ^ sg;
+    i32x4 b[PS];
+#pragma unroll
+    for (int js = 0; js < PS; ++js)
+      if (js < nps) b[js] = *reinterpret_cast<const i32x4*>(st + boff + js * Wsl::P_B);
+#pragma unroll
+    for (int jd = 0; jd < PD; ++jd)
+      if (jd < npd) {
+        const u32x4 d = (mag >> dsh[jd]) & dmk[jd];
+        const i32x4 a = __builtin_bit_cast(i32x4, ((d ^ m7) + s1) ^ sg);
+#pragma unroll
+        for (int js = 0; js < PS; ++js)
+          if (js < nps) acc[jd][js] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[js], acc[jd][js], 0, 0, 0);
+      }
+  };
+  // the ADC at a tile boundary, per pair: codes shifted by the pair's position into S, the sets cleared
+  // (every set of the pass is converted; a pair past the chunk's counts has stayed 0 and adds 0)
+  auto adc = [&]() {
+#pragma unroll
+    for (int jd = 0; jd < PD; ++jd)
+#pragma unroll
+      for (int js = 0; js < PS; ++js) {
+        const int sh = ((jd0 + jd) * P.db + (js0 + js) * P.cb) & 31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          S[0][r] += adc_code(static_cast<float>(acc[jd][js][r]), P.kf, P.qmax) * (1 << sh);
+        acc[jd][js] = zero_set();
+      }
+  };
+  pipeline(smem, STAGE_B, tile_span(z, P), P.spt, gload, compute, lstore, adc);
+
+  ip_store(S, P, P.split * P.chunks > 1 ? P.part + (int64_t)zc * P.M * P.N : nullptr, m0, n0 + nw, lh);
+}
+
 // The crossbar-tiled Convolution forward.  The array of group g
 // has the unrolled kernel as its rows, k = (ci * kh + i) * kw + j (the row order
 // of Caffe's im2col and of the weight blob), Kg = C/group * kh * kw of them,
@@ -1458,41 +1624,64 @@ int bwd_data(const float* dy, const float* w, float* dx, int M, int N, int K, co
   return launch_finish("ip_bwd_data_xbar finish", P, P.split, M, K, 1, s);
 }
 
-// The bit-sliced-weight read-out's checks (host only).  Both operands must fit
-// int8, and S (so every partial slab too) int32: |S| <= ntiles * qmax * sum_s 2^(s cb).
-constexpr int WS_PC = 4;  // slices per chunk: the one k_ip_xbar_ws instantiation
+// The bit-sliced-weight read-outs' checks (host only): rram_ip_fwd_xbar_ws and,
+// with serial, the digit-serial rram_ip_fwd_xbar_ss of db bits per digit.  Both
+// operands must fit int8, and S (so every partial slab too) int32:
+// |S| <= ntiles * qmax * sum_s 2^(s cb) (* sum_j 2^(j db)).
+constexpr int WS_PC = 4;             // slices per chunk: the one k_ip_xbar_ws instantiation
+constexpr int SS_PS = 4;             // slices per chunk of k_ip_xbar_ss<PD 3 | 2, PS 4>
 int slices_of(const rram_xbar_slices& sl) { return (sl.weight_bits - 1 + sl.cell_bits - 1) / sl.cell_bits; }
+const char* ws_who(bool serial) { return serial ? "ip_fwd_xbar_ss" : "ip_fwd_xbar_ws"; }
 
-int ws_check(int M, int N, int K, const rram_xbar_cfg* c, const rram_xbar_slices* sl, int transpose) {
+int ws_check(bool serial, int M, int N, int K, const rram_xbar_cfg* c, const rram_xbar_slices* sl, int db,
+             int transpose) {
+  const char* who = ws_who(serial);
   const int rc = check(M, N, K, c, transpose);
   if (rc) return rc;
-  RRAM_REQUIRE(c->dac_bits >= 2 && c->dac_bits <= 8, "ip_fwd_xbar_ws: dac_bits %d outside [2, 8]", c->dac_bits);
-  RRAM_REQUIRE(sl != nullptr, "ip_fwd_xbar_ws: slices is NULL");
-  RRAM_REQUIRE(sl->weight_bits >= 2 && sl->weight_bits <= 8, "ip_fwd_xbar_ws: weight_bits %d outside [2, 8]",
+  RRAM_REQUIRE(c->dac_bits >= 2 && c->dac_bits <= 8, "%s: dac_bits %d outside [2, 8]", who, c->dac_bits);
+  RRAM_REQUIRE(sl != nullptr, "%s: slices is NULL", who);
+  RRAM_REQUIRE(sl->weight_bits >= 2 && sl->weight_bits <= 8, "%s: weight_bits %d outside [2, 8]", who,
                sl->weight_bits);
   RRAM_REQUIRE(sl->cell_bits >= 1 && sl->cell_bits <= sl->weight_bits - 1,
-               "ip_fwd_xbar_ws: cell_bits %d outside [1, weight_bits - 1]", sl->cell_bits);
+               "%s: cell_bits %d outside [1, weight_bits - 1]", who, sl->cell_bits);
   RRAM_REQUIRE(std::isfinite(sl->weight_range) && sl->weight_range > 0.0f,
-               "ip_fwd_xbar_ws: weight_range must be finite and > 0");
+               "%s: weight_range must be finite and > 0", who);
   const int64_t ntiles = (K + c->rows - 1) / c->rows, qmax = (1 << (c->adc_bits - 1)) - 1;
   int64_t weight = 0;
   for (int s = 0; s < slices_of(*sl); ++s) weight += 1ll << (s * sl->cell_bits);
-  RRAM_REQUIRE(ntiles * qmax * weight < (1ll << 31),
-               "ip_fwd_xbar_ws: %lld tiles x qmax %lld x slice weights %lld overflows int32", (long long)ntiles,
-               (long long)qmax, (long long)weight);
+  if (!serial) {
+    RRAM_REQUIRE(ntiles * qmax * weight < (1ll << 31), "%s: %lld tiles x qmax %lld x slice weights %lld overflows int32",
+                 who, (long long)ntiles, (long long)qmax, (long long)weight);
+    return RRAM_OK;
+  }
+  RRAM_REQUIRE(db >= 1 && db <= c->dac_bits - 1, "%s: digit_bits %d outside [1, dac_bits - 1]", who, db);
+  int64_t digit = 0;
+  for (int j = 0; j * db < c->dac_bits - 1; ++j) digit += 1ll << (j * db);
+  RRAM_REQUIRE(ntiles * qmax * digit * weight < (1ll << 31),
+               "%s: %lld tiles x qmax %lld x digit weights %lld x slice weights %lld overflows int32", who,
+               (long long)ntiles, (long long)qmax, (long long)digit, (long long)weight);
   return RRAM_OK;
 }
 
 // The plan of a shape; ws_bytes is the caller's whole workspace, of which the
 // slice planes take plane_bytes first and the planner's slabs the rest.  The
 // chunk count is folded into the planner's workgroup count and slab size.
-size_t make_ws_plan(int M, int N, int K, const rram_xbar_cfg& c, const rram_xbar_slices& sl, int split_k,
-                    size_t ws_bytes, WsPlan& P) {
-  P = WsPlan{};
+// serial: digits of db bits on k_ip_xbar_ss's 32-row tiles, chunks on both axes
+// (3 digits x 4 slices, or 2 x 4 where that takes no more chunks: 1, 2 and 4 digits).
+size_t make_ws_plan(bool serial, int M, int N, int K, const rram_xbar_cfg& c, const rram_xbar_slices& sl, int db,
+                    int split_k, size_t ws_bytes, SsPlan& P) {
+  P = SsPlan{};
   P.M = M, P.N = N, P.K = K;
   P.ns = slices_of(sl), P.cb = sl.cell_bits;
   P.chunks = (P.ns + WS_PC - 1) / WS_PC;
-  P.tiles_m = (M + Wsl::BM - 1) / Wsl::BM;
+  if (serial) {
+    P.db = db, P.nd = (c.dac_bits - 1 + db - 1) / db;
+    P.pd = (P.nd + 2) / 3 < (P.nd + 1) / 2 ? 3 : 2;  // the fewer digit chunks, a tie to the fewer idle sets
+    P.cd = (P.nd + P.pd - 1) / P.pd, P.cs = (P.ns + SS_PS - 1) / SS_PS;
+    P.chunks = P.cd * P.cs;
+  }
+  const int bm = serial ? Ssl::BM : Wsl::BM;
+  P.tiles_m = (M + bm - 1) / bm;
   P.tiles_n = (N + BN - 1) / BN;
   const size_t plane_bytes = (size_t)P.tiles_n * ((K + KS - 1) / KS) * P.ns * Wsl::P_B;
   plan_core(P, K, c, (int64_t)P.tiles_m * P.tiles_n * P.chunks, (size_t)M * N * sizeof(int32_t) * P.chunks, split_k,
@@ -1503,25 +1692,29 @@ size_t make_ws_plan(int M, int N, int K, const rram_xbar_cfg& c, const rram_xbar
   return plane_bytes;
 }
 
-size_t ws_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int split_k) {
-  if (ws_check(M, N, K, cfg, sl, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
-  WsPlan P;
-  const size_t plane_bytes = make_ws_plan(M, N, K, *cfg, *sl, split_k, ~static_cast<size_t>(0), P);
+size_t ws_workspace(bool serial, int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int db,
+                    int split_k) {
+  if (ws_check(serial, M, N, K, cfg, sl, db, 0) != RRAM_OK || M == 0 || N == 0 || split_k < 0) return 0;
+  SsPlan P;
+  const size_t plane_bytes = make_ws_plan(serial, M, N, K, *cfg, *sl, db, split_k, ~static_cast<size_t>(0), P);
   return plane_bytes + part_bytes(P.split * P.chunks, (int64_t)M * N);
 }
 
-int ws_fwd(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int transpose,
-           const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int relu, int split_k, void* ws, size_t ws_bytes,
-           rram_stream_t st) {
-  const char* who = "ip_fwd_xbar_ws";
-  const int rc0 = ws_check(M, N, K, cfg, sl, transpose);
+// rram_ip_fwd_xbar_ws and, with serial, rram_ip_fwd_xbar_ss: the checks, the
+// plan, the activation pack, the read-out kernel and its id differ, the rest
+// (the weight pack among it) is one
+int ws_fwd(bool serial, const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+           int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* sl, int db, int relu, int split_k, void* ws,
+           size_t ws_bytes, rram_stream_t st) {
+  const char* who = ws_who(serial);
+  const int rc0 = ws_check(serial, M, N, K, cfg, sl, db, transpose);
   if (rc0) return rc0;
   RRAM_REQUIRE(split_k >= 0, "%s: negative split_k", who);
   if (M == 0 || N == 0) return RRAM_OK;
   RRAM_REQUIRE(x && w && y, "%s: NULL", who);
   RRAM_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, "%s: workspace not 16-byte aligned", who);
-  WsPlan P;
-  const size_t plane_bytes = make_ws_plan(M, N, K, *cfg, *sl, split_k, ws != nullptr ? ws_bytes : 0, P);
+  SsPlan P;
+  const size_t plane_bytes = make_ws_plan(serial, M, N, K, *cfg, *sl, db, split_k, ws != nullptr ? ws_bytes : 0, P);
   const int slabs = P.split * P.chunks;
   const int rcw = require_ws(who, ws, ws_bytes, plane_bytes + part_bytes(slabs, (int64_t)M * N), P.split, P.chunks);
   if (rcw) return rcw;
@@ -1529,17 +1722,19 @@ int ws_fwd(const float* x, const float* w, const float* bias, float* y, int M, i
   hipStream_t s = as_stream(st);
   const Steps dac = steps_of(*cfg);
 
-  if (!plan_note("xbar:pack_i8<%s>", al16(x, K) ? "vec" : "scalar")) {
-    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * Wsl::A_B;
+  if (!plan_note(serial ? "xbar:pack_sm8<%s>" : "xbar:pack_i8<%s>", al16(x, K) ? "vec" : "scalar")) {
+    const int bm = serial ? Ssl::BM : Wsl::BM;
+    const int64_t pack_b = (int64_t)P.tiles_m * P.ksteps * bm * QRB;
     char* pb = reinterpret_cast<char*>(pack_buffer(static_cast<size_t>(pack_b / 4), s));
     RRAM_REQUIRE(pb != nullptr, "%s: packed-code buffer allocation failed", who);
     P.apack = pb;
-    const int64_t units = (int64_t)P.tiles_m * Wsl::BM * P.ksteps * 4;
+    const int64_t units = (int64_t)P.tiles_m * bm * P.ksteps * 4;
     by_vec(al16(x, K), [&](auto V) {
-      hipLaunchKernelGGL(k_xbar_pack_i8<decltype(V)::value>, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb,
-                         P.ksteps, units, dac.dac_xs, dac.dac_qmax);
+      const auto pack = serial ? k_xbar_pack_sm8<decltype(V)::value> : k_xbar_pack_i8<decltype(V)::value>;
+      hipLaunchKernelGGL(pack, dim3(stream_blocks(units)), dim3(256), 0, s, x, M, K, pb, P.ksteps, units, dac.dac_xs,
+                         dac.dac_qmax);
     });
-    const int rc = launch_status("ip_fwd_xbar_ws pack");
+    const int rc = launch_status(serial ? "ip_fwd_xbar_ss pack" : "ip_fwd_xbar_ws pack");
     if (rc) return rc;
   }
   P.wplanes = static_cast<const char*>(ws);
@@ -1551,7 +1746,7 @@ int ws_fwd(const float* x, const float* w, const float* bias, float* y, int M, i
       hipLaunchKernelGGL(k_xbar_pack_wslices<decltype(V)::value>, dim3(stream_blocks(units)), dim3(256), 0, s, w, N, K,
                          static_cast<char*>(ws), P.ksteps, units, wsc, dmax, P.ns, P.cb);
     });
-    const int rc = launch_status("ip_fwd_xbar_ws weight pack");
+    const int rc = launch_status(serial ? "ip_fwd_xbar_ss weight pack" : "ip_fwd_xbar_ws weight pack");
     if (rc) return rc;
   }
   P.w = w;
@@ -1559,13 +1754,19 @@ int ws_fwd(const float* x, const float* w, const float* bias, float* y, int M, i
   P.y = y;
   P.part = slabs > 1 ? reinterpret_cast<int32_t*>(static_cast<char*>(ws) + plane_bytes) : nullptr;
   P.relu = relu;
-  if (!plan_note("xbar:ip_ws<p%d>/s%d/c%d", WS_PC, P.split, P.chunks)) {
-    hipLaunchKernelGGL(k_ip_xbar_ws<WS_PC>, dim3(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs)), dim3(256), 0, s,
-                       P);
+  if (!(serial ? plan_note("xbar:ip_ss<d%d;p%d>/s%d/c%d", P.pd, SS_PS, P.split, P.chunks)
+               : plan_note("xbar:ip_ws<p%d>/s%d/c%d", WS_PC, P.split, P.chunks))) {
+    const dim3 grid(static_cast<unsigned>(P.tiles_m * P.tiles_n * slabs));
+    if (serial && P.pd == 3)
+      hipLaunchKernelGGL((k_ip_xbar_ss<3, SS_PS>), grid, dim3(256), 0, s, P);
+    else if (serial)
+      hipLaunchKernelGGL((k_ip_xbar_ss<2, SS_PS>), grid, dim3(256), 0, s, P);
+    else
+      hipLaunchKernelGGL(k_ip_xbar_ws<WS_PC>, grid, dim3(256), 0, s, static_cast<const WsPlan&>(P));
     const int rc = launch_status(who);
     if (rc) return rc;
   }
-  return launch_finish("ip_fwd_xbar_ws finish", P, slabs, M, N, 1, s);
+  return launch_finish(serial ? "ip_fwd_xbar_ss finish" : "ip_fwd_xbar_ws finish", P, slabs, M, N, 1, s);
 }
 
 }  // namespace xb
@@ -1613,13 +1814,14 @@ int rram_ip_fwd_xbar_bs_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg
 
 size_t rram_ip_fwd_xbar_ws_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
                                      int split_k) {
-  return rram::xb::ws_workspace(M, N, K, cfg, slices, split_k);
+  return rram::xb::ws_workspace(false, M, N, K, cfg, slices, 0, split_k);
 }
 
 int rram_ip_fwd_xbar_ws(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
                         int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices, int relu,
                         int split_k, void* ws, size_t ws_bytes, rram_stream_t st) {
-  return rram::xb::ws_fwd(x, w, bias, y, M, N, K, transpose, cfg, slices, relu, split_k, ws, ws_bytes, st);
+  return rram::xb::ws_fwd(false, x, w, bias, y, M, N, K, transpose, cfg, slices, 0, relu, split_k, ws, ws_bytes,
+                          st);
 }
 
 int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
@@ -1629,6 +1831,29 @@ int rram_ip_fwd_xbar_ws_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg
   rram::PlanScope sc;
   const int rc = rram_ip_fwd_xbar_ws(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
                                      slices, 0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes, nullptr);
+  return rc ? rc : rram::copy_text(sc.text, out, cap);
+}
+
+size_t rram_ip_fwd_xbar_ss_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                     int digit_bits, int split_k) {
+  return rram::xb::ws_workspace(true, M, N, K, cfg, slices, digit_bits, split_k);
+}
+
+int rram_ip_fwd_xbar_ss(const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
+                        int transpose, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices, int digit_bits,
+                        int relu, int split_k, void* ws, size_t ws_bytes, rram_stream_t st) {
+  return rram::xb::ws_fwd(true, x, w, bias, y, M, N, K, transpose, cfg, slices, digit_bits, relu, split_k, ws,
+                          ws_bytes, st);
+}
+
+int rram_ip_fwd_xbar_ss_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, const rram_xbar_slices* slices,
+                                   int digit_bits, int x_align16, int w_align16, int split_k, size_t ws_bytes,
+                                   char* out, size_t cap) {
+  using rram::xb::fake_ptr;
+  rram::PlanScope sc;
+  const int rc = rram_ip_fwd_xbar_ss(fake_ptr(x_align16), fake_ptr(w_align16), nullptr, fake_ptr(1), M, N, K, 0, cfg,
+                                     slices, digit_bits, 0, split_k, ws_bytes ? fake_ptr(1) : nullptr, ws_bytes,
+                                     nullptr);
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 

@@ -147,6 +147,9 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
 // weight_range } } or, for a layer with a crossbar and no weight_slices of its
 // own, the Net option `crossbar_slices` ("weight_bits,cell_bits,weight_range",
 // handed down as rram_crossbar_slices).
+// *digit_bits != 0: the sliced array is read digit-serially
+// (rram_ip_fwd_xbar_ss), by weight_slices { input_digit_bits } or a fourth value
+// of the option ("weight_bits,cell_bits,weight_range,input_digit_bits").
 // bwd->rows != 0: the transposed read-out of the input gradient
 // (rram_ip_bwd_data_xbar) is asked for, by crossbar_param { backward { cols
 // adc_bits adc_range [dac_bits dac_range] } } or, for a layer with a crossbar
@@ -154,9 +157,10 @@ static void hw_param(const Msg& p, const std::string& base, int def, int& h, int
 // ("cols,adc_bits,adc_range[,dac_bits,dac_range]", handed down as
 // rram_crossbar_backward); cols goes to rram_xbar_cfg::rows.
 static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg* c, bool* bit_serial,
-                          rram_xbar_slices* sl, rram_xbar_cfg* bwd) {
+                          rram_xbar_slices* sl, int* digit_bits, rram_xbar_cfg* bwd) {
   const Msg* xp = lp.sub("crossbar_param");
   *bit_serial = false;
+  *digit_bits = 0;
   *sl = rram_xbar_slices{0, 0, 0.0f};
   *bwd = rram_xbar_cfg{0, 0, 0.0f, 0, 1.0f};
   if (xp == nullptr && !lp.has("rram_crossbar")) return false;
@@ -188,7 +192,9 @@ static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg*
     sl->weight_bits = static_cast<int32_t>(sp->integer("weight_bits", 0));
     sl->cell_bits = static_cast<int32_t>(sp->integer("cell_bits", 0));
     sl->weight_range = static_cast<float>(sp->num("weight_range", 0.0));
+    *digit_bits = static_cast<int>(sp->integer("input_digit_bits", 0));
     CAFFE_CHECK(sl->weight_bits != 0, name << ": weight_slices wants weight_bits");
+    CAFFE_CHECK(*digit_bits >= 0, name << ": input_digit_bits must not be negative");
   } else if (lp.has("rram_crossbar_slices")) {
     std::vector<double> v;
     std::stringstream ss(lp.str("rram_crossbar_slices"));
@@ -198,9 +204,10 @@ static bool read_crossbar(const Msg& lp, const std::string& name, rram_xbar_cfg*
     } catch (const std::exception&) {
       v.clear();
     }
-    CAFFE_CHECK(v.size() == 3 && v[0] != 0.0,
-                name << ": option crossbar_slices wants weight_bits,cell_bits,weight_range");
+    CAFFE_CHECK((v.size() == 3 || v.size() == 4) && v[0] != 0.0 && (v.size() == 3 || v[3] >= 0.0),
+                name << ": option crossbar_slices wants weight_bits,cell_bits,weight_range[,input_digit_bits]");
     *sl = rram_xbar_slices{static_cast<int32_t>(v[0]), static_cast<int32_t>(v[1]), static_cast<float>(v[2])};
+    if (v.size() == 4) *digit_bits = static_cast<int>(v[3]);
   }
   if (xp != nullptr) {
     c->rows = static_cast<int32_t>(xp->integer("rows", 0));
@@ -250,7 +257,8 @@ void ConvolutionLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& bottom
   bool bit_serial = false;
   rram_xbar_slices slices{};
   rram_xbar_cfg backward{};
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial, &slices, &backward);
+  int digit_bits = 0;
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &bit_serial, &slices, &digit_bits, &backward);
   CAFFE_CHECK(!bit_serial, this->name() << ": bit_serial is not served for Convolution");
   CAFFE_CHECK(slices.weight_bits == 0, this->name() << ": weight_slices is not served for Convolution");
   CAFFE_CHECK(backward.rows == 0, this->name() << ": backward is not served for Convolution");
@@ -486,7 +494,7 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
   axis_ = static_cast<int>(ip.integer("axis", 1));
   if (axis_ < 0) axis_ += bottom[0]->num_axes();
   K_ = static_cast<int>(bottom[0]->count(axis_));
-  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_, &slices_, &xbar_bwd_);
+  xbar_on_ = read_crossbar(this->layer_param_, this->name(), &xbar_, &xbar_bs_, &slices_, &xbar_db_, &xbar_bwd_);
   if (xbar_on_) {
     // the kernel library's own checks of the configuration, on a host-only plan query
     // (the bit-serial and bit-sliced ones with the workspace their chunks and planes need;
@@ -494,7 +502,12 @@ void InnerProductLayer<Dtype>::LayerSetUp(const std::vector<Blob<Dtype>*>& botto
     CAFFE_CHECK(!transpose_, this->name() << ": crossbar_param does not serve transposed weights");
     CAFFE_CHECK(!(xbar_ws() && xbar_bs_), this->name() << ": weight_slices with bit_serial is not served");
     char id[8];
-    const int rc = xbar_ws() ? rram_ip_fwd_xbar_ws_kernel_ids(
+    const int rc = xbar_ss() ? rram_ip_fwd_xbar_ss_kernel_ids(
+                                   1, N_, K_, &xbar_, &slices_, xbar_db_, 1, 1, 0,
+                                   std::max<size_t>(
+                                       1, rram_ip_fwd_xbar_ss_workspace(1, N_, K_, &xbar_, &slices_, xbar_db_, 0)),
+                                   id, sizeof id)
+                   : xbar_ws() ? rram_ip_fwd_xbar_ws_kernel_ids(
                                    1, N_, K_, &xbar_, &slices_, 1, 1, 0,
                                    std::max<size_t>(1, rram_ip_fwd_xbar_ws_workspace(1, N_, K_, &xbar_, &slices_, 0)),
                                    id, sizeof id)
@@ -557,7 +570,10 @@ void InnerProductLayer<Dtype>::Forward_gpu(const std::vector<Blob<Dtype>*>& bott
       const Dtype *xg = x + (int64_t)g * Mg * K_, *wg = w + g * group_stride_[0];
       const Dtype* bg = b ? b + g * group_stride_[1] : b;
       Dtype* yg = y + (int64_t)g * Mg * N_;
-      if (xbar_ws())  // the group's weights are sliced into the workspace by the call itself
+      if (xbar_ss())
+        RRAM_CALL(rram_ip_fwd_xbar_ss(xg, wg, bg, yg, Mg, N_, K_, 0, &xbar_, &slices_, xbar_db_, fused_relu ? 1 : 0, 0,
+                                      ws, Caffe::workspace_size(), Caffe::stream()));
+      else if (xbar_ws())  // the group's weights are sliced into the workspace by the call itself
         RRAM_CALL(rram_ip_fwd_xbar_ws(xg, wg, bg, yg, Mg, N_, K_, 0, &xbar_, &slices_, fused_relu ? 1 : 0, 0, ws,
                                       Caffe::workspace_size(), Caffe::stream()));
       else

@@ -121,6 +121,8 @@ class InnerProductLayer : public Layer<Dtype> {
     size_t f32 = std::min<size_t>((size_t)16 * M_ * N_ * sizeof(float), 256ull << 20);
     if (!xbar_on_) return f32;
     if (xbar_bwd()) f32 = std::max(f32, rram_ip_bwd_data_xbar_workspace(M_, N_, K_, &xbar_bwd_, 0));
+    if (xbar_ss())
+      return std::max(f32, rram_ip_fwd_xbar_ss_workspace(M_ / groups_, N_, K_, &xbar_, &slices_, xbar_db_, 0));
     if (xbar_ws()) return std::max(f32, rram_ip_fwd_xbar_ws_workspace(M_ / groups_, N_, K_, &xbar_, &slices_, 0));
     const auto need = xbar_bs_ ? rram_ip_fwd_xbar_bs_workspace : rram_ip_fwd_xbar_workspace;
     return std::max(f32, need(M_ / groups_, N_, K_, &xbar_, 0));
@@ -134,6 +136,10 @@ class InnerProductLayer : public Layer<Dtype> {
   // read-out rram_ip_fwd_xbar_ws, one conversion per weight slice (weight_bits 0: not asked for)
   rram_xbar_slices slices_{};
   bool xbar_ws() const { return slices_.weight_bits != 0; }
+  // weight_slices { input_digit_bits } (or the option's fourth value): the sliced array read digit-serially,
+  // rram_ip_fwd_xbar_ss, one conversion per (input digit, weight slice) pair (0: the parallel DAC)
+  int xbar_db_ = 0;
+  bool xbar_ss() const { return xbar_ws() && xbar_db_ != 0; }
   // backward (or the Net option `crossbar_backward`): the input gradient is the
   // transposed read-out rram_ip_bwd_data_xbar with this configuration, rows = the
   // array columns of one read (rows 0: not asked for, the straight-through rram_ip_bwd)

@@ -186,6 +186,9 @@ SIGNATURES = {
     "rram_ip_fwd_xbar_ws": (I, [P, P, P, P, I, I, I, I, P, P, I, I, P, SZ, P]),
     "rram_ip_fwd_xbar_ws_workspace": (SZ, [I, I, I, P, P, I]),
     "rram_ip_fwd_xbar_ws_kernel_ids": (I, [I, I, I, P, P, I, I, I, SZ, C.c_char_p, SZ]),
+    "rram_ip_fwd_xbar_ss": (I, [P, P, P, P, I, I, I, I, P, P, I, I, I, P, SZ, P]),
+    "rram_ip_fwd_xbar_ss_workspace": (SZ, [I, I, I, P, P, I, I]),
+    "rram_ip_fwd_xbar_ss_kernel_ids": (I, [I, I, I, P, P, I, I, I, I, SZ, C.c_char_p, SZ]),
     "rram_ip_bwd_data_xbar": (I, [P, P, P, I, I, I, P, I, P, SZ, P]),
     "rram_ip_bwd_data_xbar_workspace": (SZ, [I, I, I, P, I]),
     "rram_ip_bwd_data_xbar_kernel_ids": (I, [I, I, I, P, I, I, I, SZ, C.c_char_p, SZ]),

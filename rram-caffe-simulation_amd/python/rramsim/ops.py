@@ -501,6 +501,28 @@ def ip_fwd_xbar_ws_kernel_ids(M, N, K_, cfg, slices, x_align16=True, w_align16=T
                      int(w_align16), split_k, int(ws_bytes))
 
 
+def ip_fwd_xbar_ss(x, w, bias, y, M, N, K_, cfg, slices, digit_bits, transpose=False, relu=False, split_k=0,
+                   workspace=None):
+    """rram_ip_fwd_xbar_ss: the digit-serial read-out of the bit-sliced array, the input streamed digit_bits bits
+    per cycle, one ADC conversion per (input digit, weight slice) pair and crossbar tile (digit_bits in
+    [1, cfg.dac_bits - 1]; cfg.adc_range is one pair's full scale; the workspace always holds the slice planes:
+    ip_fwd_xbar_ss_workspace; split_k 0: planner)."""
+    wsb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    K.check(_lib().rram_ip_fwd_xbar_ss(_p(x), _p(w), _p(bias), _p(y), M, N, K_, int(transpose), C.byref(cfg),
+                                       C.byref(slices), digit_bits, int(relu), split_k, _p(workspace), wsb,
+                                       _stream()), "ip_fwd_xbar_ss")
+
+
+def ip_fwd_xbar_ss_workspace(M, N, K_, cfg, slices, digit_bits, split_k=0):
+    return _lib().rram_ip_fwd_xbar_ss_workspace(M, N, K_, C.byref(cfg), C.byref(slices), digit_bits, split_k)
+
+
+def ip_fwd_xbar_ss_kernel_ids(M, N, K_, cfg, slices, digit_bits, x_align16=True, w_align16=True, split_k=0,
+                              ws_bytes=0):
+    return _id_lines(_lib().rram_ip_fwd_xbar_ss_kernel_ids, M, N, K_, C.byref(cfg), C.byref(slices), digit_bits,
+                     int(x_align16), int(w_align16), split_k, int(ws_bytes))
+
+
 def ip_bwd_data_xbar(dy, w, dx, M, N, K_, cfg, split_k=0, workspace=None):
     """rram_ip_bwd_data_xbar: dx = the ADC read-out of dy . w, the array read the other way, from tiles of
     cfg.rows array columns over N (cfg: this read's own; split_k 0: planner)."""

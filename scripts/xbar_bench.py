@@ -6,13 +6,15 @@ conv2 / conv8 and a GoogLeNet 1x1, or with --serial the bit-serial
 rram_ip_fwd_xbar_bs beside rram_ip_fwd_xbar with the same DAC (dac_bits 4 and 8)
 on the InnerProduct shapes, or with --sliced the bit-sliced-weight
 rram_ip_fwd_xbar_ws (weight_bits 8, cell_bits 2 and 1) beside rram_ip_fwd_xbar
-with the same 8-bit DAC, or with --backward the transposed read-out
+with the same 8-bit DAC, or with --serial-sliced the digit-serial
+rram_ip_fwd_xbar_ss (digit_bits 1 and 2, cell_bits 2) beside rram_ip_fwd_xbar_ws
+at cell_bits 2, or with --backward the transposed read-out
 rram_ip_bwd_data_xbar beside rram_ip_bwd with only dx wanted and beside
 rram_ip_fwd_xbar on the mirrored shape.  Call times from device events (every
 launch of the call included), the two alternated in one process, the median and
 range of REPS windows of ITERS calls each.
 
-    python scripts/xbar_bench.py [--conv | --serial | --sliced | --backward] [out.txt]
+    python scripts/xbar_bench.py [--conv | --serial | --sliced | --serial-sliced | --backward] [out.txt]
 
 --sliced --shape=fc6 --cells=2 keeps one shape and one cell width, so that a
 kernel trace of the run (per-kernel totals) gives the weight pack's share of
@@ -131,6 +133,30 @@ def sliced_rows(shape=None, cells=None):
     return lines
 
 
+def serial_sliced_rows():
+    lines = ["shape  M x N x K  R B b wb db cb | serial-sliced us (min..max) ids | sliced xbar_ws us (min..max) ids | "
+             "ratio | MFMA count ratio Nd | ratio per MFMA"]
+    for name, M, N, K, R, B in SHAPES:
+        for db in (1, 2):
+            g = torch.Generator(device="cuda").manual_seed(1)
+            x = torch.randn(M, K, device="cuda", generator=g)
+            w = torch.randn(N, K, device="cuda", generator=g) * K ** -0.5
+            bias = torch.randn(N, device="cuda", generator=g)
+            y = torch.empty(M, N, device="cuda")
+            cfg, sl = ops.xbar_cfg(R, B, 4.0, 8, 4.0), ops.xbar_slices(8, 2, 4.0 * K ** -0.5)
+            wsd = torch.empty(ops.ip_fwd_xbar_ss_workspace(M, N, K, cfg, sl, db), dtype=torch.uint8, device="cuda")
+            wss = torch.empty(ops.ip_fwd_xbar_ws_workspace(M, N, K, cfg, sl), dtype=torch.uint8, device="cuda")
+            fd = lambda: ops.ip_fwd_xbar_ss(x, w, bias, y, M, N, K, cfg, sl, db, relu=True, workspace=wsd)  # noqa: E731
+            fs = lambda: ops.ip_fwd_xbar_ws(x, w, bias, y, M, N, K, cfg, sl, relu=True, workspace=wss)      # noqa: E731
+            line = row(f"{name}  {M} x {N} x {K}  {R} {B} 8 8 {db} 2", fd, fs,
+                       ops.ip_fwd_xbar_ss_kernel_ids(M, N, K, cfg, sl, db, ws_bytes=wsd.numel()),
+                       ops.ip_fwd_xbar_ws_kernel_ids(M, N, K, cfg, sl, ws_bytes=wss.numel()), 2.0 * M * N * K)
+            head, ratio, _ = line.rsplit(" | ", 2)
+            nd = -(-7 // db)
+            lines.append(f"{head} | {ratio} | {nd} | {float(ratio) / nd:.2f}")
+    return lines
+
+
 def conv_rows():
     lines = ["shape  x -> Cout k/pad/group  R B | xbar us (min..max) ids | plain us (min..max) ids | ratio | "
              "xbar share of 416.7 TFLOP/s"]
@@ -196,6 +222,8 @@ def main():
     rows = conv_rows if "--conv" in flags else serial_rows if "--serial" in flags else ip_rows
     if "--backward" in flags:
         rows = backward_rows
+    if "--serial-sliced" in flags:
+        rows = serial_sliced_rows
     if "--sliced" in flags:
         rows = lambda: sliced_rows(opt.get("shape"), int(opt.get("cells", 0)))  # noqa: E731
     text = "\n".join(rows()) + "\n"
