@@ -868,6 +868,9 @@ int rram_ip_bwd_data_xbar(const float* dy, const float* w, float* dx, int M, int
 size_t rram_ip_bwd_data_xbar_workspace(int M, int N, int K, const rram_xbar_cfg* cfg, int split_k);
 int rram_ip_bwd_data_xbar_kernel_ids(int M, int N, int K, const rram_xbar_cfg* cfg, int dy_align16, int w_align16,
                                      int split_k, size_t ws_bytes, char* out, size_t cap);
+/* rram_xbar_kernel_list (host only): every id the six crossbar *_kernel_ids
+ * queries above can return, one per line, without the /sS and /cC tails. */
+int rram_xbar_kernel_list(char* out, size_t cap);
 
 /* dw += ..., db += ... (nullable), dx = ... (nullable). */
 int rram_ip_bwd(const float* x, const float* w, const float* dy, float* dw,

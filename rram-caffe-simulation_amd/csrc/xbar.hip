@@ -1928,4 +1928,17 @@ int rram_conv2d_fwd_xbar_kernel_ids(const rram_conv_desc* d, const rram_xbar_cfg
   return rc ? rc : rram::copy_text(sc.text, out, cap);
 }
 
+// every id a launch site of this file can record, without the /sS and /cC tails
+int rram_xbar_kernel_list(char* out, size_t cap) {
+  return rram::copy_text(
+      "xbar:pack<vec>\nxbar:pack<scalar>\nxbar:pack_codes<vec>\nxbar:pack_codes<scalar>\n"
+      "xbar:pack_i8<vec>\nxbar:pack_i8<scalar>\nxbar:pack_sm8<vec>\nxbar:pack_sm8<scalar>\n"
+      "xbar:pack_wslices<vec>\nxbar:pack_wslices<scalar>\n"
+      "xbar:ip<vec>\nxbar:ip<scalar>\nxbar:ip_t<vec>\nxbar:ip_t<scalar>\n"
+      "xbar:ip_bs<vec;p4>\nxbar:ip_bs<scalar;p4>\nxbar:ip_bs<vec;p7>\nxbar:ip_bs<scalar;p7>\n"
+      "xbar:ip_ws<p4>\nxbar:ip_ss<d3;p4>\nxbar:ip_ss<d2;p4>\n"
+      "xbar:conv<vec>\nxbar:conv<scalar>\nxbar:finish\n",
+      out, cap);
+}
+
 }  // extern "C"

@@ -195,6 +195,7 @@ SIGNATURES = {
     "rram_conv2d_fwd_xbar": (I, [P, P, P, P, P, P, I, I, P, SZ, P]),
     "rram_conv2d_fwd_xbar_workspace": (SZ, [P, P, I]),
     "rram_conv2d_fwd_xbar_kernel_ids": (I, [P, P, I, I, I, SZ, C.c_char_p, SZ]),
+    "rram_xbar_kernel_list": (I, [C.c_char_p, SZ]),
     "rram_ip_rows_pack_bytes": (SZ, [I, I, I, SZ, P]),
     "rram_ip_fwd_rows": (I, [P, P, P, P, P, P, I, I, I, I, I, P, SZ, P, P]),
     "rram_relu_fwd": (I, [P, P, I64, F, P]),

@@ -557,6 +557,14 @@ def conv_fwd_xbar_kernel_ids(d, cfg, x_align16=True, w_align16=True, split_k=0, 
                      int(w_align16), split_k, int(ws_bytes))
 
 
+def xbar_kernel_list():
+    """Every id the launch sites of csrc/xbar.hip can record, without the /sS and /cC tails."""
+    n = _lib().rram_xbar_kernel_list(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    _lib().rram_xbar_kernel_list(buf, len(buf))
+    return buf.value.decode().split()
+
+
 def ip_rows_pack_bytes(M, N, K_, ws_bytes):
     """(bytes, rows per tile) of the bf16x6 engine's packed-row input form (0, 0: not served)."""
     bmc = C.c_int(0)

@@ -5,27 +5,9 @@ near-tie tiles on Gaussian inputs; identical bits under every split over K;
 and through the InnerProduct layer, the Net option and the Monte-Carlo driver."""
 import numpy as np
 import pytest
-from _xbar_cases import IP_NET, adc_tile, dac_codes, grid, run_ip, run_net
+from _xbar_cases import IP_NET, grid, ref_xbar, run_ip, run_net
 
 gpu = pytest.mark.gpu
-
-
-def ref_xbar(x, w, bias, R, bits, rng, relu=False, dac=None):
-    """(y float32, S int64, per-element count of tiles near a rounding tie, clipped anywhere)."""
-    x, w = x.astype(np.float64), w.astype(np.float64)
-    if dac:
-        q = 2 ** (dac[0] - 1) - 1
-        x = dac_codes(x, dac[1] / q, q) * (dac[1] / q)
-    qmax = 2 ** (bits - 1) - 1
-    step = float(np.float32(rng)) / qmax
-    S = np.zeros((x.shape[0], w.shape[0]), np.int64)
-    near = np.zeros(S.shape, np.int64)
-    clipped = False
-    for k0 in range(0, x.shape[1], R):
-        q, n, c = adc_tile(x[:, k0:k0 + R], w[:, k0:k0 + R], step, qmax)
-        S, near, clipped = S + q, near + n, clipped | c
-    y = S * step + (0.0 if bias is None else bias.astype(np.float64))
-    return (np.maximum(y, 0.0) if relu else y).astype(np.float32), S, near, clipped
 
 
 def run_xbar(x, w, bias, cfg_args, relu=False, split_k=0, unaligned=False):

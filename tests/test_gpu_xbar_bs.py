@@ -5,27 +5,9 @@ under every split and chunking, within the near-tie count on Gaussian inputs,
 through the InnerProduct layer, and refused where the header says so."""
 import numpy as np
 import pytest
-from _xbar_cases import IP_NET, adc_tile, dac_codes, grid, run_ip as run, run_net, same_bits
+from _xbar_cases import IP_NET, grid, ref_bs, run_ip as run, run_net, same_bits
 
 gpu = pytest.mark.gpu
-
-
-def ref_bs(x, w, bias, R, B, A, b, X, relu=False):
-    """(y float32, S int64, per-element count of near-tie (tile, plane) pairs, clipped anywhere)."""
-    x, w = x.astype(np.float64), w.astype(np.float64)
-    cmax, qmax = 2 ** (b - 1) - 1, 2 ** (B - 1) - 1
-    xs, step = float(np.float32(X)) / cmax, float(np.float32(A)) / qmax
-    c = dac_codes(x, float(np.float32(xs)), cmax).astype(np.int64)
-    S = np.zeros((x.shape[0], w.shape[0]), np.int64)
-    near = np.zeros(S.shape, np.int64)
-    clipped = False
-    for k0 in range(0, x.shape[1], R):
-        ct, wt = c[:, k0:k0 + R], w[:, k0:k0 + R]
-        for j in range(b - 1):
-            q, n, cl = adc_tile(np.sign(ct) * ((np.abs(ct) >> j) & 1), wt, step, qmax)
-            S, near, clipped = S + (q << j), near + n, clipped | cl
-    y = S * float(np.float32(step * xs)) + (0.0 if bias is None else bias.astype(np.float64))
-    return (np.maximum(y, 0.0) if relu else y).astype(np.float32), S, near, clipped
 
 
 def cfg_of(R, B, e, b, ex):

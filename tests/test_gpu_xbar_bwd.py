@@ -5,25 +5,9 @@ over N, within the near-tie count on Gaussian operands, through the layer
 message and the Net option, and the refusals without a device."""
 import numpy as np
 import pytest
-from _xbar_cases import IP_NET, adc_tile, dac_codes, dev, grid, run_net, same_bits
+from _xbar_cases import IP_NET, dev, grid, ref_bwd, run_net, same_bits
 
 gpu = pytest.mark.gpu
-
-
-def ref_bwd(dy, w, C, bits, rng, dac=None):
-    """(dx float32, S int64, per-element count of tiles near a rounding tie, clipped anywhere)."""
-    dy, w = dy.astype(np.float64), w.astype(np.float64)
-    if dac:
-        q = 2 ** (dac[0] - 1) - 1
-        dy = dac_codes(dy, dac[1] / q, q) * (dac[1] / q)
-    qmax = 2 ** (bits - 1) - 1
-    step = float(np.float32(rng)) / qmax
-    S = np.zeros((dy.shape[0], w.shape[1]), np.int64)
-    near, clipped = np.zeros(S.shape, np.int64), False
-    for n0 in range(0, dy.shape[1], C):
-        q, n, c = adc_tile(dy[:, n0:n0 + C], w[n0:n0 + C].T, step, qmax)
-        S, near, clipped = S + q, near + n, clipped | c
-    return (S * step).astype(np.float32), S, near, clipped
 
 
 def run_bwd(dy, w, cfg_args, split_k=0, unaligned=False):

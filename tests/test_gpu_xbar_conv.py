@@ -6,39 +6,9 @@ under every split over K and every batch size; within the number of near-tie
 tiles on Gaussian inputs; and through the Convolution layer and the Net option."""
 import numpy as np
 import pytest
-from _xbar_cases import dev, grid, run_net
-from test_gpu_xbar import ref_xbar
+from _xbar_cases import dev, grid, ref_conv, run_net
 
 gpu = pytest.mark.gpu
-
-
-def im2col(x, g, geom):
-    """[num * Ho * Wo][Kg] float64 columns of group g, k = (ci * kh + i) * kw + j; and (Ho, Wo)."""
-    num, C, H, W, Cout, kh, kw, ph, pw, sh, sw, dh, dw, group = geom[:14]
-    Cg = C // group
-    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    xp = np.zeros((num, Cg, H + 2 * ph, W + 2 * pw))
-    xp[:, :, ph:ph + H, pw:pw + W] = x[:, g * Cg:(g + 1) * Cg]
-    taps = [xp[:, :, i * dh:i * dh + (Ho - 1) * sh + 1:sh, j * dw:j * dw + (Wo - 1) * sw + 1:sw]
-            for i in range(kh) for j in range(kw)]
-    cols = np.stack(taps, axis=2)                                   # [num][Cg][kh*kw][Ho][Wo]
-    return cols.transpose(0, 3, 4, 1, 2).reshape(num * Ho * Wo, Cg * kh * kw), (Ho, Wo)
-
-
-def ref_conv(x, w, bias, geom, bits, rng, relu=False, dac=None):
-    """(y float32 NCHW, S, per-output count of near-tie tiles, clipped anywhere, the plain float64 convolution)."""
-    num, Cout, group, R = geom[0], geom[4], geom[13], geom[14]
-    Ng = Cout // group
-    out = [[], [], [], []]
-    clipped = False
-    for g in range(group):
-        cols, (Ho, Wo) = im2col(x, g, geom)
-        wg = w[g * Ng:(g + 1) * Ng].reshape(Ng, -1)
-        y, S, near, c = ref_xbar(cols, wg, None if bias is None else bias[g * Ng:(g + 1) * Ng], R, bits, rng, relu, dac)
-        clipped |= c
-        for o, a in zip(out, (y, S, near, cols @ wg.astype(np.float64).T)):
-            o.append(a.reshape(num, Ho, Wo, Ng).transpose(0, 3, 1, 2))
-    return tuple(np.concatenate(o, axis=1) for o in out[:3]) + (clipped, np.concatenate(out[3], axis=1))
 
 
 def desc_of(geom):

@@ -4,7 +4,7 @@ arithmetic is integers plus three rounded float operations per output, so there
 is no tolerance anywhere.  xs and ws are powers of two and kf = 2^h / 3."""
 import numpy as np
 import pytest
-from _xbar_cases import IP_NET, dev, grid, run_net, same_bits
+from _xbar_cases import IP_NET, dev, grid, ref_ws, run_net, same_bits
 
 gpu = pytest.mark.gpu
 f32 = np.float32
@@ -16,29 +16,6 @@ def cfgs(R, B, b, wb, cb, h, e=-5, f=-5):
     qmax = 2 ** (B - 1) - 1
     return ((R, B, qmax * 3.0 * 2.0 ** (e + f - h), b, (2 ** (b - 1) - 1) * 2.0 ** e),
             (wb, cb, (2 ** (wb - 1) - 1) * 2.0 ** f))
-
-
-def ref_ws(x, w, bias, cfg, sl, relu=False):
-    """(y float32, whether any ADC code clipped, max |p|)."""
-    (R, B, A, b, X), (wb, cb, Wr) = cfg, sl
-    cmax, dmax, qmax = 2 ** (b - 1) - 1, 2 ** (wb - 1) - 1, 2 ** (B - 1) - 1
-    A, X, Wr = float(f32(A)), float(f32(X)), float(f32(Wr))
-    kf, out = f32(X / cmax * (Wr / dmax) / (A / qmax)), f32(A / qmax)
-    c = np.clip(np.rint(x / f32(X / cmax)), -cmax, cmax).astype(np.int64)
-    d = np.clip(np.rint(w / f32(Wr / dmax)), -dmax, dmax).astype(np.int64)
-    S = np.zeros((x.shape[0], w.shape[0]), np.int64)
-    clipped, pmax = False, 0
-    for k0 in range(0, x.shape[1], R):
-        ct, dt = c[:, k0:k0 + R], d[:, k0:k0 + R]
-        for s in range(-(-(wb - 1) // cb)):
-            p = ct @ (np.sign(dt) * ((np.abs(dt) >> (s * cb)) & (2 ** cb - 1))).T
-            r = np.rint(p.astype(f32) * kf)
-            clipped, pmax = clipped or bool((np.abs(r) > qmax).any()), max(pmax, int(np.abs(p).max()))
-            S += np.clip(r, -qmax, qmax).astype(np.int64) << (s * cb)
-    y = S.astype(f32) * out
-    if bias is not None:
-        y = y + bias
-    return (np.maximum(y, f32(0)) if relu else y).astype(f32), clipped, pmax
 
 
 def run(x, w, bias, cfg, sl, relu=False, split_k=0, unaligned=False):
